@@ -2,6 +2,7 @@
 """Benchmark: env steps/sec (whole node) for 65,536 parallel bin-a-cube envs on 1/2/4/8 MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--total-envs 65536 | --envs-per-gpu E]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -16,6 +17,11 @@ concurrent streams).
 Envs are sharded contiguously (global ids drive the seeds); there is no collective on the data path:
 only the barrier + max-over-ranks timing reduction around the timed region.
 Rank 0 prints ONE JSON line.  See DESIGN.md §6 for the roofline bytes and the CPU baseline.
+
+A plain run does what the headline figure needs and no more: set up, warm up, time the K steps, write the last
+timed step's outputs (--dump-outputs DIR) and print the line.  --full adds every other measurement to the same
+line: HIP events around every kernel launch of the timed steps (per-kernel ms), the contact-record pool
+counters, the untimed contact-sampling steps and the CPU baseline; without it those fields are null.
 """
 import argparse
 import json
@@ -62,11 +68,18 @@ def parse(argv=None):
     p.add_argument("--envs-per-gpu", type=int, default=0, help="weak scaling: fixed envs per GPU")
     p.add_argument("--task", default="so100_cube_to_bin")
     p.add_argument("--action-pool", type=int, default=16)
-    p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample duration")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: per-kernel HIP events, the pool "
+                        "counters, contacts per env (--contact-steps untimed steps) and the CPU baseline")
+    p.add_argument("--dump-outputs", default="",
+                   help="write what the last timed step returned (obs, reward, terminated, truncated, the info "
+                        "arrays and the state) to <dir>/<name>.npy, float32 (at most 64 MB: a fixed seeded sample "
+                        "of the envs, env_index.npy, when the shard is larger)")
+    p.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU baseline sample duration")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--no-kernel-timing", action="store_true", help="skip the per-launch HIP events")
-    p.add_argument("--contact-steps", type=int, default=10, help="untimed steps sampling contacts/env")
+    p.add_argument("--no-kernel-timing", action="store_true", help="--full without the per-launch HIP events")
+    p.add_argument("--contact-steps", type=int, default=10, help="--full: untimed steps sampling contacts/env")
     p.add_argument("--fused-build", type=int, default=0, choices=[0, 2, 3],
                    help="the fused product build: 2 | 3 waves per SIMD, 0 = the library's choice by size")
     p.add_argument("--solver", default="newton", choices=["newton", "pgs"],
@@ -154,6 +167,30 @@ def workload(kind, total, world, count):
     return f"configs[2]: {per} bin-a-cube envs, joint-space ctrl, fp32 state, CubeToBin reward, auto-reset"
 
 
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def dump_outputs(env, out_dir, seed, suffix=""):
+    """--dump-outputs: what the last timed step computed, as a caller of ``SO100VecEnv.step`` receives it, one
+    float32 <name><suffix>.npy each (flags as 0 / 1): obs, reward, terminated, truncated, info's is_success and
+    final_observation (GoalEnv: achieved_goal, desired_goal too), and the state it left (qpos, qvel).  A shard
+    whose arrays pass 64 MB is sampled: a fixed sorted choice of envs drawn from ``seed``, the same for every
+    array and every run; env_index holds the shard-local ids of the rows written."""
+    import numpy as np
+    arrays = {"obs": env.obs, "reward": env.reward, "terminated": env.terminated, "truncated": env.truncated,
+              "is_success": env.success, "final_observation": env.final_obs, "qpos": env.qpos, "qvel": env.qvel}
+    if env.is_goal:
+        arrays.update(achieved_goal=env.achieved_goal, desired_goal=env.desired_goal)
+    n = env.num_envs
+    row_bytes = 4 * (1 + sum(a[0].numel() for a in arrays.values()))     # + env_index
+    keep = min(n, DUMP_MAX_BYTES // row_bytes)
+    index = np.arange(n) if keep == n else np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"env_index{suffix}.npy"), index.astype(np.float32))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a.cpu().numpy()[index].astype(np.float32))
+
+
 def main(argv=None):
     args = parse(argv)
     import torch
@@ -205,9 +242,11 @@ def main(argv=None):
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
-    if not args.no_kernel_timing:
+    kernel_timing = args.full and not args.no_kernel_timing
+    if kernel_timing:
         env.profile_enable(args.steps)      # HIP events on the launch stream around every kernel
-    env.pool_stats(reset=True)              # the fused step's contact-record pool counters, from the timed steps on
+    if args.full:
+        env.pool_stats(reset=True)          # the fused step's contact-record pool counters, from the timed steps on
     torch.cuda.synchronize(dev)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
     t0 = time.perf_counter()
@@ -223,27 +262,33 @@ def main(argv=None):
     elapsed = t1 - t0
     step_ms = ev[0].elapsed_time(ev[1]) / args.steps        # device time per env step on this stream
     solver_ms = stage_ms = float("nan")
-    pool_st = env.pool_stats()
-    if not args.no_kernel_timing:
+    if args.dump_outputs:
+        dump_outputs(env, args.dump_outputs, args.seed, "" if world == 1 else f"_rank{rank}")
+    pool_st = env.pool_stats() if args.full else None
+    if kernel_timing:
         s_ms, s_n, t_ms, t_n = env.profile_read()
         env.profile_enable(0)
         solver_ms, stage_ms = s_ms / max(s_n, 1), t_ms / max(t_n, 1)
-    # untimed: contacts per env per solver launch (the split record bytes) and contacts left out of an env's list
-    # (a checked invariant: the list holds every contact since round 4, so this is 0)
-    accum = torch.zeros(1, dtype=torch.int64, device=dev)
-    dropped = torch.zeros(1, dtype=torch.int64, device=dev)
-    for i in range(args.contact_steps):
-        env.set_action_buffer(pool[i % len(pool)])
-        env.step_async_raw()
-        env.contact_count(accum)
-        dropped += env.ncon_dropped.sum()
-    torch.cuda.synchronize(dev)
-    contacts_per_env = float(accum.item()) / max(1, args.contact_steps * count)
-    dropped_per_env_step = float(dropped.item()) / max(1, args.contact_steps * count)
+    contacts_per_env = dropped_per_env_step = None
+    if args.full:
+        # untimed: contacts per env per solver launch (the split record bytes) and contacts left out of an env's
+        # list (a checked invariant: the list holds every contact since round 4, so this is 0)
+        accum = torch.zeros(1, dtype=torch.int64, device=dev)
+        dropped = torch.zeros(1, dtype=torch.int64, device=dev)
+        for i in range(args.contact_steps):
+            env.set_action_buffer(pool[i % len(pool)])
+            env.step_async_raw()
+            env.contact_count(accum)
+            dropped += env.ncon_dropped.sum()
+        torch.cuda.synchronize(dev)
+        contacts_per_env = float(accum.item()) / max(1, args.contact_steps * count)
+        dropped_per_env_step = float(dropped.item()) / max(1, args.contact_steps * count)
     if world > 1:
         t = torch.tensor([elapsed, step_ms, solver_ms, stage_ms], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, step_ms, solver_ms, stage_ms = (float(x) for x in t)
+    if not kernel_timing:
+        solver_ms = stage_ms = None         # not measured: null in the line
 
     # sanity: the state stayed finite
     assert torch.isfinite(env.qpos).all().item(), "non-finite state after the benchmark"
@@ -272,7 +317,7 @@ def main(argv=None):
         pmc, pmc_current = load_step_traffic(count, mode, args.solver, lib_hash, kind)
         # per env step, like achieved; null unless the profile measured these kernels (the same source hash)
         traffic = pmc["hbm_bytes_per_step"] / count if (pmc and pmc_current) else None
-        if fused:
+        if fused or contacts_per_env is None:
             rec_per_launch = None
         else:
             per_env, per_con = ((PGS_RECORD_BYTES_PER_ENV, PGS_RECORD_BYTES_PER_CONTACT) if args.solver == "pgs" else
@@ -313,9 +358,9 @@ def main(argv=None):
                          "split_record_bytes_per_solver_launch": rec_per_launch, "envs_per_launch": n0,
                          "contacts_per_env": contacts_per_env,
                          "contacts_dropped_per_env_step": dropped_per_env_step,
-                         "pool_entries_taken_per_step": pool_st["taken"] / args.steps if fused else None,
-                         "pool_requests_none_free": pool_st["none_free"] if fused else None,
-                         "pool_entries_per_xcd": pool_st["entries_per_xcd"] if fused else None,
+                         "pool_entries_taken_per_step": pool_st["taken"] / args.steps if fused and pool_st else None,
+                         "pool_requests_none_free": pool_st["none_free"] if fused and pool_st else None,
+                         "pool_entries_per_xcd": pool_st["entries_per_xcd"] if fused and pool_st else None,
                          "note": ("achieved = env steps/s per GPU x SURVEY §8(d)'s algorithmic bytes per env step "
                                   "(state/action in, state/outputs out; GoalEnv 418, DR 426): nothing else is "
                                   "algorithmic. traffic = measured HBM bytes per env step from rocprofv3 "
@@ -326,7 +371,7 @@ def main(argv=None):
                                   "1024 SIMDs)")},
             "cpu_baseline": None,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(args.cpu_seconds, args.solver)
             except Exception as e:   # baseline is reported, never required for the GPU number

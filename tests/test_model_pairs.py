@@ -3,16 +3,14 @@ filters applied to the reference MJCF: the table is exactly the
 to a narrowphase, no pair more, none missing.  Filters restated from MuJoCo 3.3.3's broadphase (mj_collision /
 filter): contype/conaffinity compatibility, same weld body (which includes static-static), the
 parent-child filter (skipped for world-welded bodies), and the model's <exclude> (so_arm100.xml:165-167).
-Reads the reference MJCF, so it runs only where /root/reference exists (this container)."""
+The reference MJCF's bodies, geoms and excludes are read from tests/golden/reference_bodies.json, recorded from the
+MJCF by tests/golden/make_model_pairs.py (tools/compile_model.py's parse)."""
 import json
 import os
-import sys
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/gym_so100/assets"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference MJCF not present")
 
 
 @pytest.mark.parametrize("variant", ["joint", "ee"])
@@ -20,12 +18,11 @@ def test_pair_table_is_mujocos_filtered_pair_set(variant):
     """joint: so100_transfer_cube.xml's pairs (those not marked ee_only); ee: so100_transfer_cube_ee.xml's, the
     same scene plus the mocap body of so_arm100_ee.xml:155 (a jointless child of the world, so welded to it:
     its marker box meets neither the table, the bin nor the Base)."""
-    sys.path.insert(0, os.path.join(ROOT, "gym-so100-c_amd", "tools"))
-    from compile_model import parse
-    _, bodies, _, excludes = parse()
+    ref = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_bodies.json")))
+    bodies, excludes = ref["bodies"], {tuple(e) for e in ref["excludes"]}
     if variant == "ee":
         bodies = dict(bodies)
-        bodies["mocap_target"] = {"joints": [], "parent": "world",
+        bodies["mocap_target"] = {"joints": 0, "parent": "world",
                                   "geoms": [{"name": "mocap_target_box", "type": "box"}]}
     weld = {"world": "world"}
 

@@ -5,7 +5,7 @@ O=$1; A=$2; N=${3:-8192}; R=${4:-3}; S=${5:-200}
 mkdir -p $O
 for r in $(seq 1 $R); do
   (cd abtree/$A && timeout -k 10 200 python bench.py --total-envs $N --no-cpu-baseline --steps $S --contact-steps 0) > $O/ab_A_${N}_$r.json 2> $O/ab_A_${N}_$r.err || exit $?
-  timeout -k 10 200 python bench.py --total-envs $N --no-cpu-baseline --steps $S --contact-steps 0 > $O/ab_B_${N}_$r.json 2> $O/ab_B_${N}_$r.err || exit $?
+  timeout -k 10 200 python bench.py --full --total-envs $N --no-cpu-baseline --steps $S --contact-steps 0 > $O/ab_B_${N}_$r.json 2> $O/ab_B_${N}_$r.err || exit $?
 done
 python - "$O" "$N" "$R" <<'PY'
 import json, sys
