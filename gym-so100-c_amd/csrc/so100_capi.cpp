@@ -20,9 +20,11 @@
 #include "so100_device.h"
 
 namespace so100 {
-hipError_t launch_step(const DevModel*, int, int, int, int, Workspace&, const so100_buffers&, int, int, int, int,
+hipError_t launch_step(const DevModel*, int, int, int, int, int, Workspace&, const so100_buffers&, int, int, int, int,
                        uint64_t, int, hipStream_t, hipEvent_t*);
 int fused_build(int n, int waves, bool debug);
+bool fused_order_active(int n);
+bool fused_pack_auto(int n);
 hipError_t launch_contact_count(const Workspace&, int, uint64_t*, hipStream_t);
 hipError_t launch_contact_counts(const Workspace&, int, int32_t*, hipStream_t);
 hipError_t launch_render(const DevModel*, const float4*, const int*, const uint32_t*, int, const float*,
@@ -95,6 +97,7 @@ struct so100_env {
   uint64_t graph_clock = 0;
   float4* d_cand = nullptr;     // the hulls' support-cell candidates (DevModel::hull_cand)
   int fused_waves = 0;          // the fused product build: 2 | 3 waves per SIMD, 0 auto (so100_set_fused_build)
+  int pack = -1;                // the fused step's env packing: -1 auto, 0 off, 1 on (so100_set_env_packing)
 };
 
 // An instantiated step graph can still be running when it is evicted: wait for its last replay first.
@@ -118,6 +121,13 @@ constexpr int kFusedAutoMax = 1 << 30;
 static bool step_is_fused(const so100_env* env) {
   if (env->solver != SO100_SOLVER_NEWTON) return false;
   return env->fused < 0 ? env->n <= env->fused_max : env->fused != 0;
+}
+
+// Whether the fused step packs envs of like solver cost into the same wave (so100_order_kernel).  Auto: fused_pack_auto
+// (off at every size: no measured gain).
+static int env_packing(const so100_env* env) {
+  if (env->pack >= 0) return env->pack;
+  return so100::fused_pack_auto(env->n) ? 1 : 0;
 }
 
 static hipError_t free_chunks(so100_env* env) {
@@ -740,6 +750,7 @@ static so100_env* so100_create_impl(const so100_model* model, int n_envs, int de
   if (const char* v = getenv("SO100_GRAPH")) env->use_graph = atoi(v) != 0;
   if (const char* v = getenv("SO100_FUSED")) env->fused = atoi(v) < 0 ? -1 : atoi(v) != 0;   // A/B: 0 split, 1 fused
   if (const char* v = getenv("SO100_FUSED_MAX")) env->fused_max = atoi(v);
+  if (const char* v = getenv("SO100_PACK")) env->pack = atoi(v) < 0 ? -1 : atoi(v) != 0;   // A/B: 0 off, 1 on
   if (const char* v = getenv("SO100_FUSED_WAVES")) {
     const int w = atoi(v);
     env->fused_waves = (w == 2 || w == 3) ? w : 0;
@@ -818,13 +829,13 @@ static hipError_t enqueue_step(so100_env* env, const so100_buffers* b, int flags
   env->last_fused = step_is_fused(env);
   if (env->last_fused) {
     // one launch over all n envs (every wave runs its whole env step: no chunks needed to fill the gaps)
-    return so100::launch_step(env->d_model, env->nsubstep, env->solver, 1, env->fused_waves, env->fws, *b, env->n, env->task, flags,
+    return so100::launch_step(env->d_model, env->nsubstep, env->solver, 1, env->fused_waves, env_packing(env), env->fws, *b, env->n, env->task, flags,
                               env->max_steps, env->base_seed, env->env_offset, s, ev);
   }
   if (env->chunks.empty()) return hipErrorNotReady;      // (so100_set_step_mode allocates them)
   if (env->chunks.size() == 1) {
     Chunk& c = env->chunks[0];
-    return so100::launch_step(env->d_model, env->nsubstep, env->solver, 0, 0, c.ws, *b, c.count, env->task, flags, env->max_steps,
+    return so100::launch_step(env->d_model, env->nsubstep, env->solver, 0, 0, 0, c.ws, *b, c.count, env->task, flags, env->max_steps,
                               env->base_seed, env->env_offset, s, ev);
   }
   hipError_t e = hipEventRecord(env->fork, s);
@@ -832,13 +843,13 @@ static hipError_t enqueue_step(so100_env* env, const so100_buffers* b, int flags
     Chunk& c = env->chunks[k];
     e = hipStreamWaitEvent(c.s, env->fork, 0);
     if (e == hipSuccess)
-      e = so100::launch_step(env->d_model, env->nsubstep, env->solver, 0, 0, c.ws, offset_buffers(*b, c.start), c.count, env->task, flags,
+      e = so100::launch_step(env->d_model, env->nsubstep, env->solver, 0, 0, 0, c.ws, offset_buffers(*b, c.start), c.count, env->task, flags,
                              env->max_steps, env->base_seed, env->env_offset + c.start, c.s, nullptr);
     if (e == hipSuccess) e = hipEventRecord(c.done, c.s);
   }
   Chunk& c0 = env->chunks[0];
   if (e == hipSuccess)
-    e = so100::launch_step(env->d_model, env->nsubstep, env->solver, 0, 0, c0.ws, *b, c0.count, env->task, flags, env->max_steps,
+    e = so100::launch_step(env->d_model, env->nsubstep, env->solver, 0, 0, 0, c0.ws, *b, c0.count, env->task, flags, env->max_steps,
                            env->base_seed, env->env_offset, s, ev);
   for (size_t k = 1; k < env->chunks.size() && e == hipSuccess; k++) e = hipStreamWaitEvent(s, env->chunks[k].done, 0);
   return e;
@@ -1009,6 +1020,40 @@ static int so100_fused_build_impl(const so100_env* env, int debug) {
   return so100::fused_build(env->n, env->fused_waves, debug != 0);
 }
 
+static int so100_set_env_packing_impl(so100_env* env, int mode) {
+  if (!env) return fail("so100_set_env_packing: env is NULL");
+  if (mode < -1 || mode > 1) return fail("so100_set_env_packing: mode must be -1 (auto), 0 (off) or 1 (on)");
+  if (env->prof_cap > 0) return fail("so100_set_env_packing: disable profiling first");
+  DeviceGuard g(env->device);
+  graph_free(env);                     // captured graphs hold the other mode's order launch
+  env->pack = mode;
+  return 0;
+}
+
+static int so100_env_order_impl(so100_env* env, int32_t* out, int cap) {
+  if (!env || !out || cap < 0) return fail("so100_env_order: bad arguments");
+  if (!env->fws.eorder) return fail("so100_env_order: no fused workspace");
+  DeviceGuard g(env->device);
+  const int rows = (env->n + 3) / 4 * 4, k = cap < rows ? cap : rows;
+  if (!so100::fused_order_active(env->n)) {   // the launch takes the natural envs
+    for (int i = 0; i < k; i++) out[i] = i;
+    return 0;
+  }
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess && k > 0) e = hipMemcpy(out, env->fws.eorder, (size_t)k * sizeof(int32_t), hipMemcpyDeviceToHost);
+  return e == hipSuccess ? 0 : fail_hip("so100_env_order", e);
+}
+
+static int so100_wave_cost_impl(so100_env* env, uint32_t* out, int cap) {
+  if (!env || !out || cap < 0) return fail("so100_wave_cost: bad arguments");
+  if (!env->fws.gcost) return fail("so100_wave_cost: no fused workspace");
+  DeviceGuard g(env->device);
+  const int ng = (env->n + 3) / 4, k = cap < ng ? cap : ng;
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess && k > 0) e = hipMemcpy(out, env->fws.gcost, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost);
+  return e == hipSuccess ? 0 : fail_hip("so100_wave_cost", e);
+}
+
 static int so100_chunk_info_impl(const so100_env* env, int* nchunks, int* profiled_envs) {
   if (!env) return fail("so100_chunk_info: env is NULL");
   if (nchunks) *nchunks = (int)env->chunks.size();
@@ -1063,6 +1108,16 @@ static int so100_pool_stats_impl(so100_env* env, uint64_t* out, int reset) {
   out[1] = st[1];
   out[2] = (uint64_t)env->fws.pool_recs;
   return 0;
+}
+
+static int so100_env_cost_impl(so100_env* env, uint32_t* out, int cap) {
+  if (!env || !out || cap < 0) return fail("so100_env_cost: bad arguments");
+  if (!env->fws.ecost) return fail("so100_env_cost: no fused workspace");
+  DeviceGuard g(env->device);
+  const int k = cap < env->n ? cap : env->n;
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess && k > 0) e = hipMemcpy(out, env->fws.ecost, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost);
+  return e == hipSuccess ? 0 : fail_hip("so100_env_cost", e);
 }
 
 static int so100_goal_reward_impl(so100_env* env, int n, const float* a, const float* d, float* out, void* stream) {
@@ -1279,6 +1334,40 @@ int so100_fused_build(const so100_env* env, int debug) {
   }
 }
 
+int so100_set_env_packing(so100_env* env, int mode) {
+  try {
+    return so100_set_env_packing_impl(env, mode);
+  } catch (...) {
+    return caught("so100_set_env_packing");
+  }
+}
+
+int so100_env_packing(const so100_env* env) {
+  try {
+    if (!env) return fail("so100_env_packing: env is NULL");
+    DeviceGuard g(env->device);
+    return env_packing(env);
+  } catch (...) {
+    return caught("so100_env_packing");
+  }
+}
+
+int so100_env_order(so100_env* env, int32_t* out, int cap) {
+  try {
+    return so100_env_order_impl(env, out, cap);
+  } catch (...) {
+    return caught("so100_env_order");
+  }
+}
+
+int so100_wave_cost(so100_env* env, uint32_t* out, int cap) {
+  try {
+    return so100_wave_cost_impl(env, out, cap);
+  } catch (...) {
+    return caught("so100_wave_cost");
+  }
+}
+
 int so100_chunk_info(const so100_env* env, int* nchunks, int* profiled_envs) {
   try {
     return so100_chunk_info_impl(env, nchunks, profiled_envs);
@@ -1300,6 +1389,14 @@ int so100_pool_stats(so100_env* env, uint64_t* out, int reset) {
     return so100_pool_stats_impl(env, out, reset);
   } catch (...) {
     return caught("so100_pool_stats");
+  }
+}
+
+int so100_env_cost(so100_env* env, uint32_t* out, int cap) {
+  try {
+    return so100_env_cost_impl(env, out, cap);
+  } catch (...) {
+    return caught("so100_env_cost");
   }
 }
 

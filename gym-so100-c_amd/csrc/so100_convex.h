@@ -1251,7 +1251,8 @@ DEV void stage_convex_hit(const DevModel* __restrict__ m, EnvShared& sh, float* 
 //  * each round's hits go to their env's staging slots in list order, so each env keeps its pair order.
 // The candidate lists are the pairs passing both stages, in pair order, as before: the same contacts.
 // Returns the env's number of convex contacts (uniform across its row).  Staged contacts j >= kMaxCon go to the
-// env's HBM contact record (slot j, kMprStageOff; crec0: the record of the wave's first env).
+// env's HBM contact record (slot j, kMprStageOff; crec0: the record of the wave's first env).  sep0: the separation
+// cache of env 0; row ie's slots are those of its env id (EnvShared::env_id: the fused step's rows hold any 4 envs).
 template <bool kCells>
 DEV int mpr_contacts(const DevModel* __restrict__ m, const Workspace& w, EnvShared* shm, float* crec0, float4* sep0, int lane,
                      int grp, bool valid) {
@@ -1397,6 +1398,10 @@ DEV int mpr_contacts(const DevModel* __restrict__ m, const Workspace& w, EnvShar
   }
   const int total = c0 + c1 + c2 + c3;
   if (total == 0) return 0;
+  // fused path: the env's narrowphase items, summed over the step (Workspace::ecost)
+  if constexpr (kCells) {
+    if (lane == 0) shm[grp].cost_np += grp == 0 ? c0 : grp == 1 ? c1 : grp == 2 ? c2 : c3;
+  }
   // the list's env offsets (pre_1..3 <= 3 x 129) and the envs' staged counts (<= 129 each) packed into one word each:
   // wave-uniform values held across the narrowphase's register peak (4 + 3 separate ones were spilled)
   static_assert(3 * kItems < 1024 && kItems < 256, "packed counts");
@@ -1425,7 +1430,7 @@ DEV int mpr_contacts(const DevModel* __restrict__ m, const Workspace& w, EnvShar
       // proves the pair separated now, which is GJK's own verdict (it returns no contact for a separated pair and
       // for a touching one), so the contact list is the same; otherwise GJK (+ EPA) runs as before, from its usual
       // start.  The cache never decides a contact: a stale entry (a reset, a far move) only fails the check.
-      float4* const sc = sep0 + (size_t)ie * kSepPairs + q;
+      float4* const sc = sep0 + (size_t)shm[ie].env_id * kSepPairs + q;
       const float4 c = *sc;
       bool proved = false;
       if (c.w != 0.f) {

@@ -194,9 +194,15 @@ struct Workspace {
   int* hcount;      // [2]
   int* hlist;       // [2][kHeavyCap]
   uint32_t sub_count;   // host-side substep counter (parity)
-  // fused path (so100_fused_kernel): heavy-first wave order from the previous step's per-wave cost
-  uint32_t* gcost;  // [ngroups] shader cycles of each 4-env wave in the last fused step
-  int* order;       // [ngroups] launch order of the groups (so100_order_kernel), nullptr = natural
+  // fused path (so100_fused_kernel): heavy-first wave order, and the envs packed into waves by their previous step's
+  // cost (so100_order_kernel)
+  uint32_t* gcost;  // [ngroups] shader cycles of the wave of each launch slot in the last fused step
+  int* eorder;      // [ngroups][4] env id of each row of each launch slot (ids >= n: idle rows), nullptr = natural
+  uint32_t* pcost;  // [ngroups] order kernel scratch: the cost each quartet is sorted by
+  int* qenv;        // [ngroups][4] order kernel scratch: the quartets before the heavy-first sort
+  // [n] each env's solver cost in the last fused step, summed over its substeps: Newton loop passes << 24 (<= 255) |
+  // contacts << 12 | convex narrowphase items (<= 4095 each); nullptr: not recorded (so100_env_cost)
+  uint32_t* ecost;
   // [n][kSepPairs] the direction that last proved a convex pair separated (w = 1) or w = 0: a certificate the next
   // substep re-checks with one support evaluation before it runs GJK (results unchanged: mpr_contacts)
   float4* sep;

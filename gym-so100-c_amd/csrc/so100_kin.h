@@ -61,6 +61,10 @@ struct __attribute__((aligned(16))) EnvShared {
   float con_dist[kMaxCon];
   float mocap[7];                // EE variant: mocap pose (pos, quat wxyz)
   int rec;                       // fused path: the env's pool contact record this substep (-1: none)
+  // fused path: the env's solver cost over the step's substeps (Newton loop trips, contacts, convex narrowphase
+  // items), packed into Workspace::ecost by the epilogue; env_id: reserved for the row's env id
+  int env_id;
+  int cost_it, cost_con, cost_np;
   union {
     struct {
       ConSlot con[kMaxCon];      // geometry (collision -> Jacobian)
@@ -69,11 +73,10 @@ struct __attribute__((aligned(16))) EnvShared {
     SerialScratch ser;           // dynamics scratch (dead before collision) + link frames (live through it)
   };
 };
-// 3,184 B per env: 4 envs = 12,736 B per wave, under the 12,800 B that lets 12 workgroups share a CU's LDS
-// (allocated in 1,280-B steps: 12,928 B held the stage and fused kernels to 11 waves per CU, measured), and
-// a stride of 796 dwords (28 banks mod 64), so the 4 envs of a wave hit different LDS bank windows for the
-// same field.
-static_assert(sizeof(EnvShared) == 3184, "EnvShared: 4 per workgroup must stay within 12,800 B");
+// 3,200 B per env: 4 envs = 12,800 B per wave, the most that lets 12 workgroups share a CU's LDS
+// (allocated in 1,280-B steps: 12,928 B held the stage and fused kernels to 11 waves per CU, measured).  The stride
+// (800 dwords; 796 before the cost record's slot) measured the same on its own (profiles/pack_ab.txt, parent + pad).
+static_assert(sizeof(EnvShared) == 3200, "EnvShared: 4 per workgroup must stay within 12,800 B");
 
 // ------------------------------------------------------------------ small math (same formulas as oracle)
 DEV float dot3(const float* a, const float* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }

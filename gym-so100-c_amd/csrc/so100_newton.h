@@ -371,7 +371,7 @@ DEV void newton_diag_write_ovf(float* dbg, const float* crec, int ncon, int lane
 // same-box A/B measured the overflow paths inside the one solve at -3.0 % env steps/s at 65,536 envs)
 template <bool kOvf, class RecFn>
 DEV float newton_solve(const DevModel* __restrict__ m, const NewtonRows& r, int lane, bool valid, bool want_diag,
-                       NewtonDiag& diag, RecFn rec) {
+                       NewtonDiag& diag, RecFn rec, int& trips) {
   const bool dof = lane < SO100_NV;
   STAMP_DECL
   STAMP(-1);
@@ -469,10 +469,12 @@ DEV float newton_solve(const DevModel* __restrict__ m, const NewtonRows& r, int 
 
   bool done = !valid;
   int iters = 0;
+  trips = 0;                       // passes of the loop this env ran (its Newton steps, and the pass that found it converged)
   float last_impr = 0.f;
   for (int it = 0; it < m->iterations; it++) {
     if (__ballot(!done) == 0ull) break;
     if (!done) {
+      trips = it + 1;
       // ---- rows at the current point: forces and Hessians
       float c0, f_fr = 0.f, h_fr = 0.f, f_lim, h_lim, fc[4], hc[10];
       int zf = 0;
@@ -810,10 +812,10 @@ DEV float newton_solve(const DevModel* __restrict__ m, const NewtonRows& r, int 
 // the solve with or without the overflow paths, chosen per wave (uniform)
 template <class RecFn>
 DEV float newton_solve_any(const DevModel* __restrict__ m, const NewtonRows& r, int lane, bool valid, bool want_diag,
-                           NewtonDiag& diag, RecFn rec) {
+                           NewtonDiag& diag, RecFn rec, int& trips) {
   const int ncon_max = wave_max_row(r.ncon);
-  if (ncon_max > kMaxCon) return newton_solve<true>(m, r, lane, valid, want_diag, diag, rec);
-  return newton_solve<false>(m, r, lane, valid, want_diag, diag, rec);
+  if (ncon_max > kMaxCon) return newton_solve<true>(m, r, lane, valid, want_diag, diag, rec, trips);
+  return newton_solve<false>(m, r, lane, valid, want_diag, diag, rec, trips);
 }
 
 }  // namespace so100

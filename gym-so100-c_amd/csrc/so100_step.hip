@@ -502,7 +502,7 @@ DEV void assemble(const StageArgs& args, EnvShared& sh, int lane, int grp, int e
     // record (also its solver record); the fused path's pool record, taken only by an env whose list is longer
     float* crec = kFused ? nullptr : args.w.con + (size_t)e * kConEnv;
     float* const recbase = kFused ? args.w.pool : args.w.con + (size_t)(env - grp) * kConEnv;
-    float4* const sep = args.w.sep + (size_t)(env - grp) * kSepPairs;
+    float4* const sep = args.w.sep;   // the rows' slots by their env ids (EnvShared::env_id)
     collide<kFused>(m, args.w, recbase, sep, sh, lane, grp, valid, crec SSTAMP_PASS);
     // the env's record from here on, recomputed at each use (the contacts beyond kMaxCon are rare): not a pointer held
     // across the rows and the solve (the 3-wave build spilled it)
@@ -1031,6 +1031,7 @@ __global__ void __launch_bounds__(kThreads, kStageWaves) so100_stage_kernel(Stag
   const bool valid = env < args.n;
   const int e = valid ? env : 0;          // clamp loads for the tail group; stores are guarded
   EnvShared& sh = shm[grp];
+  if (lane == 0) sh.env_id = e;           // the identity mapping (mpr_contacts' separation cache slots)
   float qpos_r, qvel_r, warm_r, mscale, fscale, sigma;
   int elapsed0;
   uint32_t episode0;
@@ -1050,14 +1051,16 @@ __global__ void __launch_bounds__(kThreads, kStageWaves) so100_stage_kernel(Stag
 }
 
 // the fused kernel's lane / env ids inside the substep loop and the epilogue, from an opaque read of the lane's
-// position in its wave (one wave per workgroup) and the workgroup's group index (scalar)
+// position in its wave (one wave per workgroup) and the row's env id in LDS (kPack; EnvShared::env_id, the
+// prologue's: n for an idle row) or the workgroup's group index (scalar; the natural quartets)
 static_assert(kThreads == 64, "fresh_ids: one wave per workgroup");
-DEV void fresh_ids(int group, int n, int& lane, int& grp, int& env, int& e) {
+template <bool kPack>
+DEV void fresh_ids(const EnvShared* shm, int group, int n, int& lane, int& grp, int& env, int& e) {
   int t;
   asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(t));
   lane = t & (kLanes - 1);
   grp = t / kLanes;
-  env = group * kEnvsPerBlock + grp;
+  env = kPack ? shm[grp].env_id : group * kEnvsPerBlock + grp;
   e = env < n ? env : 0;
 }
 // The whole env step in one launch (Newton solver, the default): each wave runs its 4 envs through the 10
@@ -1067,12 +1070,14 @@ DEV void fresh_ids(int group, int n, int& lane, int& grp, int& env, int& e) {
 // Results are those of the split path (so100_stage_kernel + so100_newton_kernel): the same device
 // functions on the same values.  kDebug: the instantiation that also fills the debug buffer (launched when
 // the caller passes one); the other has no debug code, which costs registers in the substep loop.
-// kWaves: the waves per SIMD the register budget is sized for.  3 (168 VGPRs; 8 B/lane of scratch since round 6's
+// kWaves: the waves per SIMD the register budget is sized for.  3 (168 VGPRs with and without kPack; 8 B/lane of scratch since round 6's
 // quadratic-exact Newton stop: two floats of the arm's M row, reloaded twice per Newton step) when the
 // grid exceeds 2 waves per SIMD; a grid of at most 2 waves per SIMD (8,192 envs on 256 CUs: all waves resident at
 // once) takes the 2-wave build (its own translation unit, so100_fused2.hip, under LLVM's iterative-ILP scheduler:
 // 249-256 VGPRs, no scratch).  Register allocation only: both give the same results bit for bit.
-template <bool kDebug, int kWaves = 3>
+// kPack: the rows' envs are any 4 of the launch slot's packing block (so100_order_kernel) and each env records its
+// solver cost for the next order; without it the wave steps a natural group, as before packing.  Schedule only.
+template <bool kDebug, int kWaves = 3, bool kPack = false>
 __global__ void __launch_bounds__(kThreads, kWaves) so100_fused_kernel(const DevModel* __restrict__ model,
                                                                        StageArgs kargs) {
   // the model as a noalias kernel argument: no store of the step can clobber it, so its uniform loads stay
@@ -1099,18 +1104,29 @@ __global__ void __launch_bounds__(kThreads, kWaves) so100_fused_kernel(const Dev
   const int tid = threadIdx.x;
   const int grp0 = tid >> 4;
   const int lane0 = tid & 15;
-  const int group = args.w.order ? args.w.order[blockIdx.x] : (int)blockIdx.x;   // heavy-first (so100_order_kernel)
-  if (args.w.order) {   // the heavier half of the waves, by launch rank, issue first on their SIMD
+  if (args.w.eorder) {   // the heavier half of the waves, by launch rank, issue first on their SIMD
     const unsigned rank = blockIdx.x, ng = gridDim.x;
     if (rank < ng / 8) __builtin_amdgcn_s_setprio(3);
     else if (rank < ng / 4) __builtin_amdgcn_s_setprio(2);
     else if (rank < ng / 2) __builtin_amdgcn_s_setprio(1);
   }
-  const int env0 = group * kEnvsPerBlock + grp0;
+  // the rows' envs: the quartet so100_order_kernel gave this launch slot (heavy-first, envs of like cost together), or
+  // the natural one.  Every id outside [0, n) is an idle row (unsigned compare: no order can address outside a buffer),
+  // kept as n.
+  int env0 = blockIdx.x * kEnvsPerBlock + grp0;
+  // (natural quartets: the group from the slot's first row, a scalar load)
+  const int group = !kPack && args.w.eorder ? args.w.eorder[blockIdx.x * kEnvsPerBlock] / kEnvsPerBlock : (int)blockIdx.x;
+  if constexpr (kPack) {
+    if (args.w.eorder) env0 = args.w.eorder[env0];
+  } else {
+    env0 = group * kEnvsPerBlock + grp0;
+  }
+  if ((unsigned)env0 >= (unsigned)args.n) env0 = args.n;
   const int e0 = env0 < args.n ? env0 : 0;
   {
   const int grp = grp0, lane = lane0, e = e0;
   EnvShared& sh = shm[grp];
+  if (lane == 0) sh.env_id = env0;   // fresh_ids, mpr_contacts
   float qpos_r, qvel_r, warm_r, mscale, fscale, sigma;
   int elapsed0;
   uint32_t episode0;
@@ -1121,6 +1137,8 @@ __global__ void __launch_bounds__(kThreads, kWaves) so100_fused_kernel(const Dev
     // that found none free over the step (added to Workspace::pool_stat in the epilogue)
     sh.rec = grp == 0 ? -1 : 0;
     sh.ndrop = 0;                 // contacts left out over the step (0: the pool is sized never to run out)
+    if (kPack) sh.cost_it = sh.cost_con = 0;   // the env's solver cost over the step (Workspace::ecost)
+    sh.cost_np = 0;
   }
   const int nsub = args.m->nsubstep;
   const float h = args.m->timestep;
@@ -1128,9 +1146,9 @@ __global__ void __launch_bounds__(kThreads, kWaves) so100_fused_kernel(const Dev
     // the lane / env ids laundered per substep too: what derives from them (masks, addresses, per-lane
     // model values) is recomputed in each substep instead of hoisted and held live across the loop
     // recomputed from the wave's lane id (an opaque v_mbcnt pair, which LICM cannot hoist) and the
-    // workgroup's scalar group index: no vector value of the ids is carried across the loop
+    // row's env id in LDS: no vector value of the ids is carried across the loop
     int lane, grp, env, e;
-    fresh_ids(group, args.n, lane, grp, env, e);
+    fresh_ids<kPack>(shm, group, args.n, lane, grp, env, e);
     const bool valid = env < args.n;
     EnvShared& sh = shm[grp];
     TL_MARK(-1);
@@ -1157,6 +1175,7 @@ __global__ void __launch_bounds__(kThreads, kWaves) so100_fused_kernel(const Dev
     // the same values, and the registers are not held across collision's register peak (they were spilled there)
     qpos_r = lane < SO100_NQ ? sh.qpos[lane] : 0.f;
     qvel_r = lane < SO100_NV ? sh.qvel[lane] : 0.f;
+    if (kPack && lane == 0) sh.cost_con += nr.ncon;
     TL_MARK(0);
     NewtonDiag diag;
     const bool dbg = kDebug && args.b.debug && sub == nsub - 1;
@@ -1164,10 +1183,11 @@ __global__ void __launch_bounds__(kThreads, kWaves) so100_fused_kernel(const Dev
     // where needed, not held across the solve
     auto rec = [&]() -> float* {
       int l2, g2, en2, e2;
-      fresh_ids(group, args.n, l2, g2, en2, e2);
+      fresh_ids<kPack>(shm, group, args.n, l2, g2, en2, e2);
       return pool_rec(args.w, shm[0].rec, g2);
     };
-    const float qacc = newton_solve_any(sa.m, nr, lane, valid, dbg, diag, rec);
+    int trips;
+    const float qacc = newton_solve_any(sa.m, nr, lane, valid, dbg, diag, rec, trips);
     if (dbg) {
       int row = env;
       asm volatile("" : "+v"(row));        // not the assembly's row address (GVN would hold that across the solve)
@@ -1178,7 +1198,8 @@ __global__ void __launch_bounds__(kThreads, kWaves) so100_fused_kernel(const Dev
     {
       // the env's pool record back (its substep is done with it)
       int l2, g2, en2, e2;
-      fresh_ids(group, args.n, l2, g2, en2, e2);
+      fresh_ids<kPack>(shm, group, args.n, l2, g2, en2, e2);
+      if (kPack && l2 == 0) shm[g2].cost_it += trips;
       if (l2 == 0 && g2 == 0) {
         const int ent = shm[0].rec;
         if (ent >= 0) pool_release(args.w, ent);
@@ -1193,7 +1214,7 @@ __global__ void __launch_bounds__(kThreads, kWaves) so100_fused_kernel(const Dev
     // fresh ids again: the epilogue's store addresses must not be the prologue's load addresses (CSE would
     // hold those across the substep loop)
     int lane, grp, env, e;
-    fresh_ids(group, args.n, lane, grp, env, e);
+    fresh_ids<kPack>(shm, group, args.n, lane, grp, env, e);
     const bool valid = env < args.n;
     EnvShared& sh = shm[grp];
     euler_update(sh, lane, h, warm_r, qpos_r, qvel_r);
@@ -1203,7 +1224,9 @@ __global__ void __launch_bounds__(kThreads, kWaves) so100_fused_kernel(const Dev
     uint32_t ep0 = args.b.episode ? args.b.episode[e] : 0u;
     final_stage(args, sh, lane, grp, env, e, valid, qpos_r, qvel_r, warm_r, el0, ep0);
     if (valid && lane == 0 && args.b.ncon_dropped) args.b.ncon_dropped[env] = (uint32_t)sh.ndrop;
-    if (args.w.gcost && lane == 0 && grp == 0) args.w.gcost[group] = (uint32_t)(__builtin_amdgcn_s_memtime() - cost_t0);
+    if (kPack && valid && lane == 0 && args.w.ecost)
+      args.w.ecost[env] = (uint32_t)min(sh.cost_it, 255) << 24 | (uint32_t)min(sh.cost_con, 4095) << 12 | (uint32_t)min(sh.cost_np, 4095);
+    if (args.w.gcost && lane == 0 && grp == 0) args.w.gcost[kPack ? (int)blockIdx.x : group] = (uint32_t)(__builtin_amdgcn_s_memtime() - cost_t0);
     if (lane == 0 && grp == 0 && args.w.pool_stat) {
       const int took = shm[1].rec, none = shm[2].rec;
       if (took) __hip_atomic_fetch_add(args.w.pool_stat, (unsigned long long)took, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1242,7 +1265,7 @@ struct ResetArgs {
 // scheduler (Makefile): +3.8 % at 8,192 envs, same box (profiles/r05_ab_sched_8192.txt); the 3-wave build spills under
 // that scheduler (220 B/lane), so it and everything else stay on the default one.
 #ifndef SO100_FUSED2_TU
-hipError_t launch_fused2(const DevModel* m, const StageArgs& a, dim3 grid, hipStream_t s);
+hipError_t launch_fused2(const DevModel* m, const StageArgs& a, dim3 grid, hipStream_t s, int pack);
 
 __global__ void __launch_bounds__(kThreads) so100_reset_kernel(ResetArgs args) {
   __shared__ EnvShared shm[kEnvsPerBlock];
@@ -1349,14 +1372,77 @@ hipError_t launch_newton(const DevModel* m, const Workspace& w, float* qacc_out,
 // arrays (an env's qpos is 52 B, its reward 4 B: a 64-B line spans 1-16 envs) through one L2, which merges them before
 // write-back, instead of one partial line per XCD (round 4's global order scattered neighbours over the 8 L2s).
 // A counting sort on a 9-bit cost key (5 exponent bits from 2^1 up, 4 mantissa bits, 6 % buckets), one workgroup per
-// range.  The order changes the schedule, never a result.
+// range.
+// Packing (pack != 0): a wave runs its 4 envs in lockstep, every Newton loop to the last env's last pass and every
+// contact loop to the longest list, so the quartets themselves are re-formed too: inside each block of kPackBlock
+// consecutive envs (aligned to the range start: the block's envs share the cache lines today's 16 neighbouring groups
+// do) the envs are ranked by descending key, the previous step's packed solver cost (Workspace::ecost; ties: env id;
+// the ids past n last), and the ranked list is cut into quartets.  A quartet's cost is predicted from its members'
+// keys, the largest Newton pass count and the sum of the narrowphase items (the wave-shared narrowphase is additive),
+// and the heavy-first sort runs on that.  Without packing the quartets are the natural groups and their cost the one
+// measured in the last step (gcost, per launch slot: mapped back through the order that launch used).
+// Output: eorder[4 slot + row] = env id of row `row` of launch slot `slot` (ids >= n: idle rows).
+// The order changes the schedule, never a result.
 constexpr int kOrderXcd = 8;
 constexpr int kOrderKeys = 512;
 constexpr int kOrderMinGroups = 256;           // the order also sets the waves' issue priority
+#ifndef SO100_PACK_BLOCK
+#define SO100_PACK_BLOCK 64
+#endif
+constexpr int kPackBlock = SO100_PACK_BLOCK;
+constexpr int kOrderThreads = 1024;
+static_assert(kPackBlock % 64 == 0 && kPackBlock <= 1024, "a packing block: whole waves of one workgroup");
+// predicted wave cost (shader cycles, the unit of gcost) of a quartet from its keys: a least-squares fit of the measured
+// wave costs at 65,536 envs (profiles/pack_predictor_65536.txt)
+// (a wave's Newton loops and contact loops run to its largest env's, its narrowphase items add up)
+constexpr float kPackCost0 = 400000.f, kPackCostPass = 12000.f, kPackCostCon = 17000.f, kPackCostItem = 11000.f;
 // blocks of XCD x (b % 8 == x) of a grid of ng blocks; range x starts at the sum of those of the XCDs before it
-DEV int order_cnt(int ng, int x) { return (ng - x + kOrderXcd - 1) / kOrderXcd; }
-__global__ void __launch_bounds__(1024) so100_order_kernel(const uint32_t* __restrict__ gcost, int ng,
-                                                           int* __restrict__ order) {
+__host__ __device__ inline int order_cnt(int ng, int x) { return (ng - x + kOrderXcd - 1) / kOrderXcd; }
+// The quartets of one packing block per workgroup (a thread per env): qenv[4 g + row] and pcost[g] for the block's
+// quartets g (of its range's [start, start + cnt)).  The blocks of range x follow those of the ranges before it.
+DEV int pack_blocks(int ng, int x) { return (order_cnt(ng, x) * kEnvsPerBlock + kPackBlock - 1) / kPackBlock; }
+__global__ void __launch_bounds__(kPackBlock) so100_pack_kernel(const uint32_t* __restrict__ ecost,
+                                                                uint32_t* __restrict__ pcost, int* __restrict__ qenv,
+                                                                int ng, int n) {
+  __shared__ unsigned long long bkey[kPackBlock];   // the block's keys (+ 1; 0: an id past n), then ranked
+  const int t = threadIdx.x;
+  int b = blockIdx.x, start = 0, x = 0;
+  for (; x < kOrderXcd - 1 && b >= pack_blocks(ng, x); x++) {
+    b -= pack_blocks(ng, x);
+    start += order_cnt(ng, x);
+  }
+  const int nloc = order_cnt(ng, x) * kEnvsPerBlock;
+  const int li = b * kPackBlock + t, id = start * kEnvsPerBlock + li;
+  const unsigned long long mine = (li < nloc && id < n) ? (unsigned long long)ecost[id] + 1ull : 0ull;
+  bkey[t] = mine;
+  __syncthreads();
+  int rank = 0;
+  for (int j = 0; j < kPackBlock; j++) {
+    const unsigned long long o = bkey[j];
+    rank += (o > mine || (o == mine && j < t)) ? 1 : 0;
+  }
+  __syncthreads();
+  bkey[rank] = mine;
+  if (li < nloc) qenv[start * kEnvsPerBlock + b * kPackBlock + rank] = id;
+  __syncthreads();
+  if (li < nloc && t % kEnvsPerBlock == 0) {
+    uint32_t passes = 0u, items = 0u, cons = 0u;
+    for (int k = 0; k < kEnvsPerBlock; k++) {
+      const unsigned long long o = bkey[t + k];
+      if (o == 0ull) continue;
+      const uint32_t key = (uint32_t)(o - 1ull);
+      passes = max(passes, key >> 24);
+      cons = max(cons, (key >> 12) & 4095u);
+      items += key & 4095u;
+    }
+    pcost[start + li / kEnvsPerBlock] =
+        (uint32_t)(kPackCost0 + kPackCostPass * (float)passes + kPackCostCon * (float)cons + kPackCostItem * (float)items);
+  }
+}
+__global__ void __launch_bounds__(kOrderThreads) so100_order_kernel(const uint32_t* __restrict__ gcost,
+                                                                    const uint32_t* __restrict__ pcost,
+                                                                    const int* __restrict__ qenv,
+                                                                    int* __restrict__ eorder, int ng, int pack) {
   // one workgroup per XCD range (round 6: the 8 ranges sort independently, in parallel; one workgroup sorting all
   // of them took 15.6 us per step at 65,536 envs, 0.6 % of the step)
   __shared__ int hist[kOrderKeys];
@@ -1365,14 +1451,15 @@ __global__ void __launch_bounds__(1024) so100_order_kernel(const uint32_t* __res
   int start = 0;
   for (int y = 0; y < x; y++) start += order_cnt(ng, y);
   const int cnt = order_cnt(ng, x);
+  const uint32_t* __restrict__ cost = pack ? pcost : gcost;   // (without packing: the natural groups' measured costs)
   auto key = [&](int g) {
-    const uint32_t u = __float_as_uint((float)gcost[g]);
+    const uint32_t u = __float_as_uint((float)cost[g]);
     const int ex = min(max((int)(u >> 23) - 128, 0), 31);
     return (kOrderKeys - 1) - ((ex << 4) | (int)((u >> 19) & 15u));
   };
   if (t < kOrderKeys) hist[t] = 0;
   __syncthreads();
-  for (int i = t; i < cnt; i += 1024) atomicAdd(&hist[key(start + i)], 1);
+  for (int i = t; i < cnt; i += kOrderThreads) atomicAdd(&hist[key(start + i)], 1);
   __syncthreads();
   const int own = t < kOrderKeys ? hist[t] : 0;
   if (t < kOrderKeys) part[t] = own;
@@ -1385,12 +1472,26 @@ __global__ void __launch_bounds__(1024) so100_order_kernel(const uint32_t* __res
   }
   if (t < kOrderKeys) hist[t] = part[t] - own;   // the bucket's first rank
   __syncthreads();
-  for (int i = t; i < cnt; i += 1024) {
+  for (int i = t; i < cnt; i += kOrderThreads) {
     const int g = start + i;
     const int r = atomicAdd(&hist[key(g)], 1);   // rank in range x
-    order[kOrderXcd * r + x] = g;
+    int4 q = make_int4(4 * g, 4 * g + 1, 4 * g + 2, 4 * g + 3);
+    if (pack) q = reinterpret_cast<const int4*>(qenv)[g];
+    reinterpret_cast<int4*>(eorder)[kOrderXcd * r + x] = q;
   }
 }
+// the order buffer before the first launch: range x's groups in their natural order on XCD x's slots
+static void natural_order(int ng, int* eorder) {
+  int start = 0;
+  for (int x = 0; x < kOrderXcd; x++) {
+    const int cnt = order_cnt(ng, x);
+    for (int r = 0; r < cnt; r++)
+      for (int k = 0; k < kEnvsPerBlock; k++) eorder[(kOrderXcd * r + x) * kEnvsPerBlock + k] = (start + r) * kEnvsPerBlock + k;
+    start += cnt;
+  }
+}
+// whether a fused launch of n envs takes its rows from the order buffer (else: the natural envs)
+bool fused_order_active(int n) { return (n + kEnvsPerBlock - 1) / kEnvsPerBlock > kOrderMinGroups; }
 
 // compute units of the current device (cached per device; 0 if the query fails: the 3-wave build then)
 static int device_cus() {
@@ -1415,9 +1516,20 @@ int fused_build(int n, int waves, bool debug) {
   return ng <= 2 * 4 * device_cus() ? 2 : 3;
 }
 
+// Packing in auto mode: off at every size.  Measured on one box against the natural quartets (profiles/pack_ab.txt):
+// the mean wave runs 4.6 % fewer cycles at 65,536 envs (profiles/pack_fit_65536.txt) but the step gains nothing (the
+// launch ends with a drain of a few late long waves, and the packed waves are the longest), and it loses 3.5 % at 32,768
+// envs, 10 % at 16,384 and 12 % at 8,192, where the step ends with its longest wave.  so100_set_env_packing(env, 1) or
+// SO100_PACK=1 turns it on.
+bool fused_pack_auto(int n) {
+  (void)n;
+  return false;
+}
+
 // fused (Newton only): the whole env step as one so100_fused_kernel launch; ev then takes 2 events.
 // waves: the fused product build (fused_build).
-hipError_t launch_step(const DevModel* m, int nsubstep, int solver, int fused, int waves, Workspace& w,
+// pack: the fused step re-forms its quartets from the envs' last costs (so100_order_kernel).
+hipError_t launch_step(const DevModel* m, int nsubstep, int solver, int fused, int waves, int pack, Workspace& w,
                        const so100_buffers& b, int n, int task, int flags, int max_steps, uint64_t base_seed,
                        int env_offset, hipStream_t s, hipEvent_t* ev) {
   StageArgs a{m, b, w, n, task, flags, max_steps, base_seed, env_offset, 0, 0};
@@ -1426,22 +1538,30 @@ hipError_t launch_step(const DevModel* m, int nsubstep, int solver, int fused, i
   if (ev) (void)hipEventRecord(ev[k++], s);
   if (fused && solver == SO100_SOLVER_NEWTON) {
     const int ng = (int)grid.x;
-    if (w.order && w.gcost && ng > kOrderMinGroups) {
+    if (w.eorder && w.gcost && w.ecost && w.pcost && w.qenv && ng > kOrderMinGroups) {
       if (ev) (void)hipEventRecord(ev[0], s);   // the order kernel stays outside the timed launch
-      hipLaunchKernelGGL(so100_order_kernel, dim3(kOrderXcd), dim3(1024), 0, s, w.gcost, ng, w.order);
+      if (pack) {
+        int nb = 0;
+        for (int x = 0; x < kOrderXcd; x++) nb += (order_cnt(ng, x) * kEnvsPerBlock + kPackBlock - 1) / kPackBlock;
+        hipLaunchKernelGGL(so100_pack_kernel, dim3(nb), dim3(kPackBlock), 0, s, w.ecost, w.pcost, w.qenv, ng, n);
+      }
+      hipLaunchKernelGGL(so100_order_kernel, dim3(kOrderXcd), dim3(kOrderThreads), 0, s, w.gcost, w.pcost, w.qenv, w.eorder,
+                         ng, pack);
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) return e;
       if (ev) (void)hipEventRecord(ev[0], s);
     } else {
-      a.w.order = nullptr;
+      a.w.eorder = nullptr;
     }
     const int build = fused_build(n, waves, b.debug != nullptr);
 #ifndef SO100_RU_FUSED3_ONLY   // (Makefile ru3: only the 3-wave product build, for register-allocation work)
-    if (build == 1) hipLaunchKernelGGL(so100_fused_kernel<true>, grid, dim3(kThreads), 0, s, m, a);
-    else if (build == 2) (void)launch_fused2(m, a, grid, s);
+    if (build == 1 && pack) hipLaunchKernelGGL((so100_fused_kernel<true, 3, true>), grid, dim3(kThreads), 0, s, m, a);
+    else if (build == 1) hipLaunchKernelGGL((so100_fused_kernel<true, 3, false>), grid, dim3(kThreads), 0, s, m, a);
+    else if (build == 2) (void)launch_fused2(m, a, grid, s, pack);
+    else if (!pack) hipLaunchKernelGGL((so100_fused_kernel<false, 3, false>), grid, dim3(kThreads), 0, s, m, a);
     else
 #endif
-    hipLaunchKernelGGL((so100_fused_kernel<false, 3>), grid, dim3(kThreads), 0, s, m, a);
+    hipLaunchKernelGGL((so100_fused_kernel<false, 3, true>), grid, dim3(kThreads), 0, s, m, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (ev) (void)hipEventRecord(ev[k++], s);
@@ -1545,14 +1665,15 @@ hipError_t alloc_workspace(int n, Workspace* w) {
 hipError_t free_workspace(Workspace* w) {
   hipError_t r = hipSuccess;
   for (void* p : {(void*)w->hdr, (void*)w->con, (void*)w->gflag, (void*)w->hcount, (void*)w->hlist, (void*)w->gcost,
-                  (void*)w->order, (void*)w->sep, (void*)w->pool, (void*)w->pool_bm, (void*)w->pool_stat}) {
+                  (void*)w->eorder, (void*)w->pcost, (void*)w->qenv, (void*)w->sep, (void*)w->pool, (void*)w->pool_bm, (void*)w->pool_stat, (void*)w->ecost}) {
     if (!p) continue;
     hipError_t e = hipFree(p);
     if (r == hipSuccess) r = e;
   }
   w->hdr = w->con = nullptr;
-  w->gflag = w->gcost = nullptr;
-  w->hcount = w->hlist = w->order = nullptr;
+  w->gflag = w->gcost = w->ecost = nullptr;
+  w->hcount = w->hlist = w->eorder = w->qenv = nullptr;
+  w->pcost = nullptr;
   w->sep = nullptr;
   w->pool = nullptr;
   w->pool_bm = nullptr;
@@ -1599,7 +1720,18 @@ hipError_t alloc_fused_workspace(int n, Workspace* w) {
   if (e == hipSuccess) e = hipMemset(w->pool_stat, 0, 2 * sizeof(unsigned long long));
   if (e == hipSuccess) e = hipMalloc(&w->gcost, ng * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMemset(w->gcost, 0, ng * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc(&w->order, ng * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&w->eorder, ng * kEnvsPerBlock * sizeof(int));
+  if (e == hipSuccess) {
+    std::vector<int> nat(ng * kEnvsPerBlock);
+    natural_order((int)ng, nat.data());
+    e = hipMemcpy(w->eorder, nat.data(), nat.size() * sizeof(int), hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess) e = hipMalloc(&w->qenv, ng * kEnvsPerBlock * sizeof(int));
+  if (e == hipSuccess) e = hipMemset(w->qenv, 0, ng * kEnvsPerBlock * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&w->pcost, ng * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMemset(w->pcost, 0, ng * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(&w->ecost, (size_t)n * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMemset(w->ecost, 0, (size_t)n * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMalloc(&w->sep, (size_t)n * kSepPairs * sizeof(float4));
   if (e == hipSuccess) e = hipMemset(w->sep, 0, (size_t)n * kSepPairs * sizeof(float4));
   if (e != hipSuccess) (void)free_workspace(w);
@@ -1631,8 +1763,9 @@ hipError_t launch_goal_reward(const DevModel* m, int n, const float* a, const fl
 }
 
 #else   // SO100_FUSED2_TU
-hipError_t launch_fused2(const DevModel* m, const StageArgs& a, dim3 grid, hipStream_t s) {
-  hipLaunchKernelGGL((so100_fused_kernel<false, 2>), grid, dim3(kThreads), 0, s, m, a);
+hipError_t launch_fused2(const DevModel* m, const StageArgs& a, dim3 grid, hipStream_t s, int pack) {
+  if (pack) hipLaunchKernelGGL((so100_fused_kernel<false, 2, true>), grid, dim3(kThreads), 0, s, m, a);
+  else hipLaunchKernelGGL((so100_fused_kernel<false, 2, false>), grid, dim3(kThreads), 0, s, m, a);
   return hipGetLastError();
 }
 #endif  // SO100_FUSED2_TU

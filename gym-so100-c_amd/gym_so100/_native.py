@@ -46,7 +46,7 @@ class NativeLibraryError(RuntimeError):
 _lib = None
 
 
-ABI_VERSION = 17         # include/so100.h SO100_ABI_VERSION
+ABI_VERSION = 18         # include/so100.h SO100_ABI_VERSION
 HULL_CELLG = 8           # SO100_HULL_CELLG
 HULL_NCELL = 6 * HULL_CELLG * HULL_CELLG
 
@@ -88,11 +88,17 @@ def load():
     lib.so100_hull_cells.argtypes = [_P, _P, _P, ctypes.c_int]
     lib.so100_set_fused_build.argtypes = [_P, ctypes.c_int]
     lib.so100_fused_build.argtypes = [_P, ctypes.c_int]
+    lib.so100_set_env_packing.argtypes = [_P, ctypes.c_int]
+    lib.so100_env_packing.argtypes = [_P]
+    lib.so100_env_order.argtypes = [_P, _P, ctypes.c_int]
+    lib.so100_env_cost.argtypes = [_P, _P, ctypes.c_int]
+    lib.so100_wave_cost.argtypes = [_P, _P, ctypes.c_int]
     for fn in ("so100_destroy", "so100_num_envs", "so100_configure", "so100_reset", "so100_step",
                "so100_goal_reward", "so100_eval_reward", "so100_spawn_pose", "so100_unnormalize",
                "so100_profile_enable", "so100_profile_read", "so100_contact_count", "so100_contact_counts",
                "so100_pool_stats", "so100_chunk_info", "so100_render_mesh", "so100_render", "so100_set_step_mode", "so100_step_mode", "so100_hull_cells",
-               "so100_set_fused_build", "so100_fused_build"):
+               "so100_set_fused_build", "so100_fused_build", "so100_set_env_packing", "so100_env_packing",
+               "so100_env_order", "so100_env_cost", "so100_wave_cost"):
         getattr(lib, fn).restype = ctypes.c_int
     lib.so100_struct_sizes.argtypes = [_P, _P]
     lib.so100_struct_sizes.restype = ctypes.c_int
@@ -114,7 +120,8 @@ EXPORTED_SYMBOLS = ("so100_abi_version", "so100_last_error", "so100_source_hash"
                     "so100_contact_count", "so100_contact_counts", "so100_pool_stats", "so100_chunk_info", "so100_render_mesh",
                     "so100_render",
                     "so100_set_step_mode", "so100_step_mode", "so100_hull_cells", "so100_set_fused_build",
-                    "so100_fused_build")
+                    "so100_fused_build", "so100_set_env_packing", "so100_env_packing", "so100_env_order",
+                    "so100_env_cost", "so100_wave_cost")
 
 
 def source_hash():

@@ -452,6 +452,40 @@ class SO100VecEnv:
     def fused_build(self, waves):
         _native.check(self.lib.so100_set_fused_build(self._handle, int(waves or 0)), "so100_set_fused_build")
 
+    @property
+    def env_packing(self):
+        """Whether the next fused step packs envs of like solver cost into the same wave: a schedule
+        only, every result is bit for bit the same with it on or off.  Set True / False, or None for auto (the default:
+        off at every size, where it measured no gain; include/so100.h so100_set_env_packing)."""
+        return bool(self.lib.so100_env_packing(self._handle))
+
+    @env_packing.setter
+    def env_packing(self, mode):
+        _native.check(self.lib.so100_set_env_packing(self._handle, -1 if mode is None else int(bool(mode))),
+                      "so100_set_env_packing")
+
+    def env_order(self):
+        """The order the last fused launch used (int32 [4 * ceil(N / 4)]): entry 4 * slot + row is the env that row
+        `row` of launch slot `slot` stepped; ids >= N are idle rows.  Synchronises the device."""
+        out = np.zeros((self.num_envs + 3) // 4 * 4, dtype=np.int32)
+        _native.check(self.lib.so100_env_order(self._handle, out.ctypes.data_as(ctypes.c_void_p), out.size), "so100_env_order")
+        return out
+
+    def env_cost(self):
+        """Each env's solver cost in the last packed fused step, summed over its substeps (the packing key), as three int
+        arrays: Newton loop passes (saturating at 255), contacts, convex narrowphase items (at 4095).  Synchronises
+        the device."""
+        out = np.zeros(self.num_envs, dtype=np.uint32)
+        _native.check(self.lib.so100_env_cost(self._handle, out.ctypes.data_as(ctypes.c_void_p), out.size), "so100_env_cost")
+        return (out >> 24).astype(np.int64), ((out >> 12) & 4095).astype(np.int64), (out & 4095).astype(np.int64)
+
+    def wave_cost(self):
+        """Shader cycles of each wave of the last fused step (uint32 [ceil(N / 4)]): by launch slot with packing on, by
+        natural group (env // 4) with it off.  Synchronises the device."""
+        out = np.zeros((self.num_envs + 3) // 4, dtype=np.uint32)
+        _native.check(self.lib.so100_wave_cost(self._handle, out.ctypes.data_as(ctypes.c_void_p), out.size), "so100_wave_cost")
+        return out
+
     def chunk_info(self):
         """(chunks, envs of chunk 0): the env split of a step; profile_read times chunk 0's launches."""
         k, n0 = ctypes.c_int(0), ctypes.c_int(0)

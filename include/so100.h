@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SO100_ABI_VERSION 17  /* 17: so100_pool_stats (the fused step's contact-record pool, sized never to run out);  16: so100_source_hash;  15: the EE variant's mocap marker box collides (SO100_NGEOM 16, SO100_NPAIR 209, SO100_NCON_MAX 643, debug stride 3,922);  14: no per-env contact cap (SO100_NCON_MAX: every pair at its collider's maximum), debug stride 3,436 (SO100_DBG_OVF), ncon_dropped always 0, status -3 for a caught C++ exception;  13: so100_buffers.ep_return / ep_final / ep_accum (device-side episode statistics);  12: so100_model.convex (GJK/EPA mesh collider, MuJoCo 3.3.3 default), box-box up to 8 contacts, cube-table one convex contact;  11: so100_buffers.ncon_dropped, debug stride 160 (contact friction forces), so100_set_fused_build;  10: so100_hull_cells (MPR support lookup);  9: pad/link-hull pairs (SO100_NPAIR 191);  8: fused step kernel, so100_set_step_mode;  7: reward64 buffer;  6: Base hull + pad pairs (SO100_NPAIR 155, SO100_NHULL_ALL 10); 5: EE/mocap weld, render API */
+#define SO100_ABI_VERSION 18  /* 18: env packing of the fused step (so100_set_env_packing, so100_env_packing, so100_env_order, so100_env_cost, so100_wave_cost);  17: so100_pool_stats (the fused step's contact-record pool, sized never to run out);  16: so100_source_hash;  15: the EE variant's mocap marker box collides (SO100_NGEOM 16, SO100_NPAIR 209, SO100_NCON_MAX 643, debug stride 3,922);  14: no per-env contact cap (SO100_NCON_MAX: every pair at its collider's maximum), debug stride 3,436 (SO100_DBG_OVF), ncon_dropped always 0, status -3 for a caught C++ exception;  13: so100_buffers.ep_return / ep_final / ep_accum (device-side episode statistics);  12: so100_model.convex (GJK/EPA mesh collider, MuJoCo 3.3.3 default), box-box up to 8 contacts, cube-table one convex contact;  11: so100_buffers.ncon_dropped, debug stride 160 (contact friction forces), so100_set_fused_build;  10: so100_hull_cells (MPR support lookup);  9: pad/link-hull pairs (SO100_NPAIR 191);  8: fused step kernel, so100_set_step_mode;  7: reward64 buffer;  6: Base hull + pad pairs (SO100_NPAIR 155, SO100_NHULL_ALL 10); 5: EE/mocap weld, render API */
 
 /* tasks (gym_so100/__init__.py:4-32 ids; single_arm.py task classes) */
 #define SO100_TASK_CUBE_TO_BIN 0          /* gym_so100/SO100CubeToBin-v0, TimeLimit 700 */
@@ -188,6 +188,24 @@ int so100_contact_counts(so100_env* env, int32_t* out, void* stream);
  * pool holds as many entries as the XCD can hold fused waves resident), out[2] = entries per XCD; the first two summed
  * over the steps since so100_create or the last reset != 0 call.  Synchronises the device (a benchmark / test hook). */
 int so100_pool_stats(so100_env* env, uint64_t* out, int reset);
+/* (ABI 18) Env packing of the fused step: a wave steps 4 envs in lockstep and waits for the slowest
+ * of them in every solver loop, so before each launch the envs of every block of 64 consecutive envs are ranked by
+ * their last step's solver cost and cut into the waves' quartets.  A schedule only: every result is bit for bit the
+ * same with it on or off.  mode: -1 auto (default; off at every size: it measured no gain at 65,536 envs and slower
+ * below), 0 off, 1 on; the SO100_PACK environment variable sets the initial value.
+ * so100_env_packing returns what the next fused step uses (0 | 1). */
+int so100_set_env_packing(so100_env* env, int mode);
+int so100_env_packing(const so100_env* env);
+/* The order the last fused launch used, to out (HOST int32 [min(cap, 4 * ceil(N / 4))]): out[4 * slot + row] = the env
+ * that row `row` of launch slot `slot` stepped; ids >= N are idle rows.  Synchronises the device (a test hook). */
+int so100_env_order(so100_env* env, int32_t* out, int cap);
+/* Each env's solver cost in the last packed fused step (recorded only while packing is on), summed over its substeps,
+ * to out (HOST uint32 [min(cap, N)]): Newton loop passes << 24 (saturating at 255) | contacts << 12 | convex
+ * narrowphase items (saturating at 4095 each): the packing key.  so100_wave_cost: the shader cycles of each wave of
+ * the last fused step (HOST uint32 [min(cap, ceil(N / 4))]), indexed by launch slot with packing on and by natural
+ * group (env / 4) with it off.  Both synchronise the device (profiling hooks). */
+int so100_env_cost(so100_env* env, uint32_t* out, int cap);
+int so100_wave_cost(so100_env* env, uint32_t* out, int cap);
 
 /* ---- camera images: the reference's default observation, obs_type
  * "so100_pixels_agent_pos" (gym_so100/__init__.py:4-32) = the `top` camera rendered by dm_control
