@@ -208,14 +208,19 @@ class TF:
                 f"{int(self.drop_gpu.sum())} oracle {int(self.drop_ora.sum())}")
 
 
-def _tf_run(env, model, o64, o32, steps, act_fn, task=0, mocap=None, res=None, ens=False):
+def _tf_run(env, model, o64, o32, steps, act_fn, task=0, mocap=None, res=None, ens=False, oracle_act=None):
     """Teacher-forced steps: each starts the product kernels, the debug build and both oracles from the
-    GPU's fp32 state (act_fn(step) -> [n, 6] float32 actions).  ens: also the ensemble floor (TF.eqv / eqa), ENS64
+    GPU's fp32 state (act_fn(step) -> [n, 6] float32 actions).  model: one model, or a sequence of n models, one per env
+    (domain randomisation: every oracle run of env i, the floors' included, uses models[i]).  oracle_act(step, i,
+    act_i) -> the action the oracles of env i are fed in place of act_i (the action noise the kernel adds).
+    ens: also the ensemble floor (TF.eqv / eqa), ENS64
     independent 1-ulp perturbations of each state through the fp64 oracle and ENS32 through the fp32 restatement, and
     the FMA-contracted fp32 restatement on the state itself (TF.mqv / mqa).  The floors of a state are computed from
     the oracle runs alone, before the GPU's result is read."""
     res = res or TF()
     n = env.num_envs
+    models = list(model) if isinstance(model, (list, tuple)) else [model] * n
+    assert len(models) == n
     d64, d32, dp, dq = o64.new_data(), o32.new_data(), o64.new_data(), o64.new_data()
     prng = np.random.default_rng(12345)
     erng = np.random.default_rng(777)
@@ -235,6 +240,8 @@ def _tf_run(env, model, o64, o32, steps, act_fn, task=0, mocap=None, res=None, e
         # the oracle side of every state first: the fp64 answer and every floor (single runs and the ensemble)
         ora = []
         for i in range(n):
+            model = models[i]
+            act_i = act[i] if oracle_act is None else np.asarray(oracle_act(step, i, act[i]), np.float32)
             for o, d in ((o64, d64), (o32, d32)):
                 o.set_state(d, q0[i], v0[i], w0[i])
                 setm(d, i)
@@ -245,9 +252,9 @@ def _tf_run(env, model, o64, o32, steps, act_fn, task=0, mocap=None, res=None, e
             setm(dq, i)
             o64.call("so100o_fwd_position", model, dq)
             near0 = any(abs(dq.con[c].dist) < NEAR0 for c in range(dq.ncon))
-            _, r, _ = o64.env_step(model, d64, task, act[i])
-            o32.env_step(model, d32, task, act[i])
-            o64.env_step(model, dp, task, act[i])
+            _, r, _ = o64.env_step(model, d64, task, act_i)
+            o32.env_step(model, d32, task, act_i)
+            o64.env_step(model, dp, task, act_i)
             oq, ov = o64.get_state(d64)[:2]
             fq, fv = o32.get_state(d32)[:2]
             s64, s32, sp = o64.last_solve(d64), o32.last_solve(d32), o64.last_solve(dp)
@@ -259,7 +266,7 @@ def _tf_run(env, model, o64, o32, steps, act_fn, task=0, mocap=None, res=None, e
                     qp, vp = perturbed(i, q0, v0)
                     o64.set_state(dp, qp, vp, w0[i])
                     setm(dp, i)
-                    o64.env_step(model, dp, task, act[i])
+                    o64.env_step(model, dp, task, act_i)
                     pe, fe, _, qae, _ = o64.last_solve(dp)
                     eq.append(_rel(o64.get_state(dp)[1], ov))
                     ea.append(_rel(qae, s64[3]))
@@ -271,7 +278,7 @@ def _tf_run(env, model, o64, o32, steps, act_fn, task=0, mocap=None, res=None, e
                     qp, vp = perturbed(i, q0, v0)
                     o32.set_state(d32, qp, vp, w0[i])
                     setm(d32, i)
-                    o32.env_step(model, d32, task, act[i])
+                    o32.env_step(model, d32, task, act_i)
                     eq.append(_rel(o32.get_state(d32)[1], ov))
                     pe, fe, _, qae, _ = o32.last_solve(d32)
                     ea.append(_rel(qae, s64[3]))
@@ -281,7 +288,7 @@ def _tf_run(env, model, o64, o32, steps, act_fn, task=0, mocap=None, res=None, e
                 dm = om.new_data()
                 om.set_state(dm, q0[i], v0[i], w0[i])
                 setm(dm, i)
-                om.env_step(model, dm, task, act[i])
+                om.env_step(model, dm, task, act_i)
                 o_.update(eq=eq, ea=ea, ef=ef, mqv=_rel(om.get_state(dm)[1], ov), mqa=_rel(om.last_solve(dm)[3], s64[3]))
             ora.append(o_)
         # then the GPU, graded against them
