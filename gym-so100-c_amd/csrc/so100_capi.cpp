@@ -28,7 +28,7 @@ bool fused_pack_auto(int n);
 hipError_t launch_contact_count(const Workspace&, int, uint64_t*, hipStream_t);
 hipError_t launch_contact_counts(const Workspace&, int, int32_t*, hipStream_t);
 hipError_t launch_render(const DevModel*, const float4*, const int*, const uint32_t*, int, const float*,
-                         const uint8_t*, const so100_camera&, int, int, int, uint8_t*, hipStream_t);
+                         const uint8_t*, const so100_camera&, int, int, int, const so100_image_out&, hipStream_t);
 hipError_t alloc_workspace(int, Workspace*);
 hipError_t alloc_fused_workspace(int, Workspace*);
 hipError_t free_workspace(Workspace*);
@@ -1188,18 +1188,47 @@ static int so100_render_mesh_impl(so100_env* env, const float* tri, const int* b
   return 0;
 }
 
-static int so100_render_impl(so100_env* env, const float* qpos, const uint8_t* mask, const so100_camera* cam, int width,
-                 int height, uint8_t* out, void* stream) {
-  if (!env || !qpos || !cam || !out) return fail("so100_render: bad arguments");
-  if (env->r_ntri <= 0) return fail("so100_render: no render mesh (so100_render_mesh)");
+// the one render launch behind so100_render (hwc alone) and so100_render_to; `who` names the entry point in errors
+static int render_launch(const char* who, so100_env* env, const float* qpos, const uint8_t* mask, const so100_camera* cam,
+                         int width, int height, const so100_image_out& o, void* stream) {
+  char msg[160];
+  auto bad = [&](const char* what) {
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    return fail(msg);
+  };
+  if (!env || !qpos || !cam) return bad("bad arguments");
+  if (!o.hwc && !o.chw && !o.flat) return bad("no sink (hwc, chw and flat are all NULL)");
+  if (env->r_ntri <= 0) return bad("no render mesh (so100_render_mesh)");
   if (width <= 0 || height <= 0 || width > 4096 || (long)width * height > (1L << 22))
-    return fail("so100_render: bad image size (width <= 4096, width*height <= 2^22)");
+    return bad("bad image size (width <= 4096, width*height <= 2^22)");
+  if (o.flat && o.flat_pitch < (int64_t)3 * width * height) return bad("flat_pitch < 3*H*W");
   if (cam->nlight < 0 || cam->nlight > SO100_MAX_LIGHTS || !(cam->fovy > 0.f && cam->fovy < 180.f))
-    return fail("so100_render: bad camera");
+    return bad("bad camera");
   DeviceGuard g(env->device);
   hipError_t e = so100::launch_render(env->d_model, env->r_tri, env->r_body, env->r_rgb, env->r_ntri, qpos, mask, *cam,
-                                      env->n, width, height, out, (hipStream_t)stream);
-  return e == hipSuccess ? 0 : fail_hip("so100_render", e);
+                                      env->n, width, height, o, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip(who, e);
+}
+
+static int so100_render_impl(so100_env* env, const float* qpos, const uint8_t* mask, const so100_camera* cam, int width,
+                 int height, uint8_t* out, void* stream) {
+  if (!out) return fail("so100_render: bad arguments");
+  so100_image_out o{(uint32_t)sizeof(so100_image_out), out, nullptr, nullptr, 0};
+  return render_launch("so100_render", env, qpos, mask, cam, width, height, o, stream);
+}
+
+static int so100_render_to_impl(so100_env* env, const float* qpos, const uint8_t* mask, const so100_camera* cam,
+                                int width, int height, const so100_image_out* out, void* stream) {
+  // the struct's size first: nothing else of *out is read before it is known to be this library's layout
+  if (!out) return fail("so100_render_to: NULL out");
+  if (out->size != sizeof(so100_image_out)) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "so100_render_to: so100_image_out.size %u, expected %zu", out->size,
+             sizeof(so100_image_out));
+    return fail(msg);
+  }
+  if (!env) return fail("so100_render_to: NULL env");
+  return render_launch("so100_render_to", env, qpos, mask, cam, width, height, *out, stream);
 }
 
 
@@ -1455,6 +1484,15 @@ int so100_render(so100_env* env, const float* qpos, const uint8_t* mask, const s
     return so100_render_impl(env, qpos, mask, cam, width, height, out, stream);
   } catch (...) {
     return caught("so100_render");
+  }
+}
+
+int so100_render_to(so100_env* env, const float* qpos, const uint8_t* mask, const so100_camera* cam, int width,
+                    int height, const so100_image_out* out, void* stream) {
+  try {
+    return so100_render_to_impl(env, qpos, mask, cam, width, height, out, stream);
+  } catch (...) {
+    return caught("so100_render_to");
   }
 }
 

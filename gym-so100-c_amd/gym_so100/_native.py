@@ -39,6 +39,15 @@ class SO100Camera(ctypes.Structure):
                 ("light_diffuse", ctypes.c_float * SO100_MAX_LIGHTS)]
 
 
+class SO100ImageOut(ctypes.Structure):
+    """Mirror of ``so100_image_out`` (include/so100.h): the sinks of one ``so100_render_to`` launch, NULL = not
+    written.  ``size`` is set to the mirror's size, which the callee checks against its own."""
+    _fields_ = [("size", ctypes.c_uint32), ("hwc", _P), ("chw", _P), ("flat", _P), ("flat_pitch", ctypes.c_int64)]
+
+    def __init__(self, hwc=None, chw=None, flat=None, flat_pitch=0):
+        super().__init__(ctypes.sizeof(SO100ImageOut), hwc, chw, flat, flat_pitch)
+
+
 class NativeLibraryError(RuntimeError):
     pass
 
@@ -46,7 +55,7 @@ class NativeLibraryError(RuntimeError):
 _lib = None
 
 
-ABI_VERSION = 18         # include/so100.h SO100_ABI_VERSION
+ABI_VERSION = 19         # include/so100.h SO100_ABI_VERSION
 HULL_CELLG = 8           # SO100_HULL_CELLG
 HULL_NCELL = 6 * HULL_CELLG * HULL_CELLG
 
@@ -85,6 +94,8 @@ def load():
     lib.so100_step_mode.argtypes = [_P]
     lib.so100_render_mesh.argtypes = [_P, _P, _P, _P, ctypes.c_int]
     lib.so100_render.argtypes = [_P, _P, _P, ctypes.POINTER(SO100Camera), ctypes.c_int, ctypes.c_int, _P, _P]
+    lib.so100_render_to.argtypes = [_P, _P, _P, ctypes.POINTER(SO100Camera), ctypes.c_int, ctypes.c_int,
+                                    ctypes.POINTER(SO100ImageOut), _P]
     lib.so100_hull_cells.argtypes = [_P, _P, _P, ctypes.c_int]
     lib.so100_set_fused_build.argtypes = [_P, ctypes.c_int]
     lib.so100_fused_build.argtypes = [_P, ctypes.c_int]
@@ -96,7 +107,7 @@ def load():
     for fn in ("so100_destroy", "so100_num_envs", "so100_configure", "so100_reset", "so100_step",
                "so100_goal_reward", "so100_eval_reward", "so100_spawn_pose", "so100_unnormalize",
                "so100_profile_enable", "so100_profile_read", "so100_contact_count", "so100_contact_counts",
-               "so100_pool_stats", "so100_chunk_info", "so100_render_mesh", "so100_render", "so100_set_step_mode", "so100_step_mode", "so100_hull_cells",
+               "so100_pool_stats", "so100_chunk_info", "so100_render_mesh", "so100_render", "so100_render_to", "so100_set_step_mode", "so100_step_mode", "so100_hull_cells",
                "so100_set_fused_build", "so100_fused_build", "so100_set_env_packing", "so100_env_packing",
                "so100_env_order", "so100_env_cost", "so100_wave_cost"):
         getattr(lib, fn).restype = ctypes.c_int
@@ -118,7 +129,7 @@ EXPORTED_SYMBOLS = ("so100_abi_version", "so100_last_error", "so100_source_hash"
                     "so100_configure", "so100_reset", "so100_step", "so100_goal_reward", "so100_eval_reward",
                     "so100_spawn_pose", "so100_unnormalize", "so100_profile_enable", "so100_profile_read",
                     "so100_contact_count", "so100_contact_counts", "so100_pool_stats", "so100_chunk_info", "so100_render_mesh",
-                    "so100_render",
+                    "so100_render", "so100_render_to",
                     "so100_set_step_mode", "so100_step_mode", "so100_hull_cells", "so100_set_fused_build",
                     "so100_fused_build", "so100_set_env_packing", "so100_env_packing", "so100_env_order",
                     "so100_env_cost", "so100_wave_cost")

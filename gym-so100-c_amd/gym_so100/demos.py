@@ -52,8 +52,11 @@ class DemoRecorder:
         torch = _torch()
         ids = torch.as_tensor(self.env_ids, device=self.venv.device)
         # one device->host copy per field for the recorded envs; pixels to channel-first like
-        # VecTransposeImage
-        pix = obs["pixels"].index_select(0, ids).permute(0, 3, 1, 2).contiguous().cpu().numpy()
+        # VecTransposeImage (an env built with channels_first already draws them so)
+        pix = obs["pixels"].index_select(0, ids)
+        if not getattr(self.venv, "channels_first", False):
+            pix = pix.permute(0, 3, 1, 2)
+        pix = pix.contiguous().cpu().numpy()
         pos = obs["agent_pos"].index_select(0, ids).cpu().numpy().astype(np.float32)
         act = torch.as_tensor(actions).to(self.venv.device, torch.float32).index_select(0, ids).cpu().numpy()
         rew = reward.index_select(0, ids).cpu().numpy().astype(np.float32)

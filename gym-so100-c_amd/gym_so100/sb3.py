@@ -16,8 +16,21 @@ vectorised envs: one object stepping N envs on the GPU with SB3's VecEnv contrac
 
 When stable-baselines3 is importable the class derives from its ``VecEnv`` (so ``VecNormalize`` and
 ``isinstance`` checks accept it); otherwise it is a duck-typed equivalent.  The physics stays on the
-GPU; this layer only moves the [N,15] observation and the per-env scalars to host numpy, which SB3's
+GPU; this layer only moves the observation and the per-env scalars to host numpy, which SB3's
 numpy interface requires.
+
+``obs_type="so100_pixels_agent_pos"`` is the observation the reference's scripts train on (train_sac.py:294-310):
+
+* the three arm tasks observe ``{"pixels": uint8 [H,W,3], "agent_pos": float32 [6]}`` (reference env.py:50-66).
+  With ``channels_first=True`` the image is [3,H,W], drawn in that layout by the render kernel, so the script's
+  ``VecTransposeImage`` line is dropped; with the default the reference's wrapper stack applies as written;
+* the GoalEnv observes ``"observation"`` = the flattened image / 255 followed by agent_pos, float32 [3HW+6]
+  (env.py:219-238, 267-270), filled on the device by the render launch (``SO100VecEnv(flat_pixels=True)``).
+
+The image (or flattened) tensor reaches the host by one asynchronous copy into pinned memory and one stream
+synchronisation per step.  Two pinned buffers alternate: **the image array of an observation returned by
+``reset()`` / ``step()`` stays valid through the next ``step()`` and is overwritten by the one after it** (SB3's
+collectors hold ``_last_obs`` across one step); copy it to keep it longer.
 """
 import time
 
@@ -42,14 +55,41 @@ class SO100SB3VecEnv(_VecEnvBase):
     metadata = {"render_modes": []}
 
     def __init__(self, num_envs, task="so100_cube_to_bin", device="cuda:0", seed=0, max_episode_steps=None,
-                 domain_randomization=None, env_offset=0, iterations=None, solver="newton"):
+                 domain_randomization=None, env_offset=0, iterations=None, solver="newton", obs_type="so100_state",
+                 observation_width=640, observation_height=480, channels_first=False):
+        self.pixel_obs = obs_type == "so100_pixels_agent_pos"
+        kw = {}
+        if self.pixel_obs:
+            kw = dict(obs_type=obs_type, observation_width=observation_width, observation_height=observation_height,
+                      channels_first=channels_first, flat_pixels=task == "so100_goal")
+        elif obs_type != "so100_state":
+            raise NotImplementedError(f"obs_type={obs_type!r}: 'so100_state' or 'so100_pixels_agent_pos'")
+        elif channels_first:
+            raise ValueError("channels_first needs obs_type='so100_pixels_agent_pos'")
         self.venv = SO100VecEnv(num_envs, task=task, device=device, seed=seed, max_episode_steps=max_episode_steps,
                                 autoreset=True, domain_randomization=domain_randomization, env_offset=env_offset,
-                                iterations=iterations, solver=solver, episode_stats=True)
+                                iterations=iterations, solver=solver, episode_stats=True, **kw)
         self._t0 = time.time()
         n = self.venv.num_envs
         obs_box = spaces.Box(low=-np.inf, high=np.inf, shape=(15,), dtype=np.float32)
-        if self.venv.is_goal:
+        goal_box = spaces.Box(low=-np.inf, high=np.inf, shape=(3,), dtype=np.float32)
+        self._host = None
+        if self.pixel_obs:
+            import torch
+            r = self.venv.renderer
+            src = self.venv.pixels_flat if self.venv.is_goal else self.venv.pixels
+            # the two pinned host buffers the image / flattened observation alternates between
+            self._host = [torch.empty(src.shape, dtype=src.dtype, pin_memory=True) for _ in range(2)]
+            self._host_i = 0
+            if self.venv.is_goal:
+                obs_space = spaces.Dict({
+                    "observation": spaces.Box(low=-np.inf, high=np.inf, shape=(src.shape[1],), dtype=np.float32),
+                    "achieved_goal": goal_box, "desired_goal": goal_box})
+            else:
+                obs_space = spaces.Dict({
+                    "pixels": spaces.Box(low=0, high=255, shape=tuple(r.image_shape), dtype=np.uint8),
+                    "agent_pos": spaces.Box(low=-10.0, high=10.0, shape=(6,), dtype=np.float32)})
+        elif self.venv.is_goal:
             obs_space = spaces.Dict({
                 "observation": obs_box,
                 "achieved_goal": spaces.Box(low=-np.inf, high=np.inf, shape=(3,), dtype=np.float32),
@@ -57,13 +97,16 @@ class SO100SB3VecEnv(_VecEnvBase):
         else:
             obs_space = obs_box
         act_space = spaces.Box(low=-1, high=1, shape=(6,), dtype=np.float32)
+        if self.pixel_obs:
+            self.metadata = {"render_modes": ["rgb_array"]}
+            self.render_mode = "rgb_array"          # read back by SB3's VecEnv.__init__ through get_attr
         if _VecEnvBase is not object:
             super().__init__(n, obs_space, act_space)
         else:
             self.num_envs = n
             self.observation_space = obs_space
             self.action_space = act_space
-            self.render_mode = None
+            self.render_mode = "rgb_array" if self.pixel_obs else None
         self._next_seeds = None
         self._actions = None
         self.reset_infos = [{} for _ in range(n)]
@@ -107,8 +150,18 @@ class SO100SB3VecEnv(_VecEnvBase):
             final = _np(v.final_obs[done_t])
             if v.is_goal:
                 fgoal = _np(prev_goal[done_t])
+            if self.pixel_obs:
+                fpix = _np(v.final_pixels[done_t])           # only the done envs' images, gathered on the device
+                if v.is_goal:                                # _flatten_observation (env.py:267-270), in numpy
+                    fflat = np.concatenate([fpix.reshape(idx.size, -1).astype(np.float32) / np.float32(255.0),
+                                            final[:, 9:15]], axis=1)
             for k, i in enumerate(idx):
-                if v.is_goal:
+                if self.pixel_obs and v.is_goal:
+                    term_obs = {"observation": fflat[k], "achieved_goal": final[k, 0:3].copy(),
+                                "desired_goal": fgoal[k]}
+                elif self.pixel_obs:
+                    term_obs = {"pixels": fpix[k], "agent_pos": final[k, 9:15].copy()}
+                elif v.is_goal:
                     term_obs = {"observation": final[k], "achieved_goal": final[k, 0:3].copy(),
                                 "desired_goal": fgoal[k]}
                 else:
@@ -131,10 +184,23 @@ class SO100SB3VecEnv(_VecEnvBase):
         self.venv.close()
 
     def get_images(self):
-        return [None] * self.num_envs      # camera renders are out of scope
+        """Pixel observations: the N current camera images as [H,W,3] uint8 arrays (transposing views of the host
+        copy when the env stores them channel-first).  State observations draw no camera: N times None."""
+        if not self.pixel_obs:
+            return [None] * self.num_envs
+        img = _np(self.venv.pixels)
+        if self.venv.channels_first:
+            img = img.transpose(0, 2, 3, 1)
+        return [img[i] for i in range(self.num_envs)]
 
     def render(self, mode=None):
-        return None
+        """Pixel observations: the current images, tiled by SB3's own ``VecEnv.render`` when SB3 is importable,
+        else stacked [N,H,W,3].  State observations: None."""
+        if not self.pixel_obs:
+            return None
+        if _VecEnvBase is not object:
+            return super().render(mode)
+        return np.stack(self.get_images())
 
     def _indices(self, indices):
         if indices is None:
@@ -169,6 +235,17 @@ class SO100SB3VecEnv(_VecEnvBase):
 
     # ------------------------------------------------------------------ helpers
     def _obs_np(self, obs):
+        if self._host is not None:
+            # the large tensor: one asynchronous copy into the pinned buffer of this step, one synchronisation
+            import torch
+            big = "observation" if self.venv.is_goal else "pixels"
+            host = self._host[self._host_i]
+            self._host_i ^= 1
+            host.copy_(obs[big], non_blocking=True)
+            out = {k: _np(t) for k, t in obs.items() if k != big}
+            torch.cuda.current_stream(self.venv.device).synchronize()
+            out[big] = host.numpy()
+            return out
         if isinstance(obs, dict):
             return {k: _np(t) for k, t in obs.items()}
         return _np(obs)

@@ -98,17 +98,31 @@ class SO100VecEnv:
             (mask ``info["_episode"]``), and ``episode_statistics()`` reduces the totals on demand.
         nsubstep: physics substeps per env step (default: the reference's 10, control_timestep / timestep);
             1 makes an env step one mj_step + the final mj_step1 (the parity tests' per-substep checks).
+        channels_first: pixel observations only: ``pixels``, ``final_pixels`` and
+            ``info["final_observation"]["pixels"]`` are [N,3,H,W], the layout SB3's image policies take, written
+            by the render kernel itself (no transpose pass).  ValueError with task="so100_goal", whose flattened
+            observation is the reference's HWC order.
+        flat_pixels: pixel observations only: keep ``pixels_flat``, a persistent float32 [N, 3HW+6] tensor:
+            every full render fills its image part (the [H,W,3] bytes / 255 as numpy divides them, env.py:267-270)
+            in the launch that fills ``pixels``, and reset / step copy agent_pos into its last six columns.  The
+            GoalEnv then returns it as ``"observation"`` (the same tensor every call, overwritten by the next step);
+            without the flag that observation is built by torch on every call.
     """
 
     def __init__(self, num_envs, task="so100_cube_to_bin", obs_type="so100_state", device="cuda:0", seed=0,
                  max_episode_steps=None, autoreset=True, domain_randomization=None, env_offset=0,
                  iterations=None, debug=False, solver="newton", observation_width=640, observation_height=480,
-                 variant="joint", reward64=False, nsubstep=None, convex="epa", episode_stats=False):
+                 variant="joint", reward64=False, nsubstep=None, convex="epa", episode_stats=False, channels_first=False,
+                 flat_pixels=False):
         torch = _torch()
         if obs_type not in ("so100_state", "so100_pixels_agent_pos"):
             raise NotImplementedError(f"obs_type={obs_type!r}: 'so100_state' or 'so100_pixels_agent_pos'")
         if task not in _native.TASKS:
             raise NotImplementedError(task)    # env.py:117-118
+        if channels_first and task == "so100_goal":
+            raise ValueError("channels_first: the GoalEnv's flattened pixel observation is HWC (env.py:267-270)")
+        if (channels_first or flat_pixels) and obs_type != "so100_pixels_agent_pos":
+            raise ValueError("channels_first / flat_pixels need obs_type='so100_pixels_agent_pos'")
         self.lib = _native.load()
         self.num_envs = int(num_envs)
         self.task = task
@@ -169,12 +183,17 @@ class SO100VecEnv:
         self._fill_buffers()
         self._seeds = torch.zeros(n, dtype=i32, device=d)
         self._mask = torch.zeros(n, dtype=torch.uint8, device=d)
-        self.pixels = self.final_pixels = self.renderer = None
+        self.pixels = self.final_pixels = self.renderer = self.pixels_flat = None
+        self.channels_first = bool(channels_first)
         if obs_type == "so100_pixels_agent_pos":
             from .render import CameraRenderer
-            self.renderer = CameraRenderer(self, observation_width, observation_height)
+            self.renderer = CameraRenderer(self, observation_width, observation_height,
+                                           channels_first=self.channels_first)
             self.pixels = self.renderer.pixels
             self.final_pixels = torch.zeros_like(self.pixels) if self.autoreset else None
+            if flat_pixels:
+                self._npix = 3 * self.renderer.width * self.renderer.height
+                self.pixels_flat = torch.zeros(n, self._npix + 6, dtype=f32, device=d)
 
     # ------------------------------------------------------------------ plumbing
     def _fill_buffers(self):
@@ -254,7 +273,7 @@ class SO100VecEnv:
         _native.check(self.lib.so100_reset(self._handle, ctypes.byref(self._buf), mask_p, seeds_p, self._stream()),
                       "so100_reset")
         if self.renderer is not None:
-            self.renderer.render()
+            self._render_all()
         info = {"is_success": torch.zeros_like(self.success)}
         return self._observation(), info
 
@@ -320,8 +339,15 @@ class SO100VecEnv:
             self.renderer.render(out=self.final_pixels, mask=self._mask)
             _native.check(self.lib.so100_reset(self._handle, ctypes.byref(self._buf), _native.ptr(self._mask), None,
                                                s), "so100_reset")
-        self.renderer.render()
+        self._render_all()
         return done
+
+    def _render_all(self):
+        """Draw every env into ``pixels``; with flat_pixels the same launch fills the image part of ``pixels_flat``,
+        and agent_pos goes into its last six columns."""
+        self.renderer.render(flat=self.pixels_flat)
+        if self.pixels_flat is not None:
+            self.pixels_flat[:, self._npix:].copy_(self.obs[:, 9:15])
 
     def episode_statistics(self, clear=False):
         """Totals of the episodes finished since construction (or the last ``clear``), reduced over the envs
@@ -344,6 +370,9 @@ class SO100VecEnv:
         if self.renderer is not None:
             agent_pos = self.obs[:, 9:15]                       # qpos[:6] float32 (single_arm.py:45-50)
             if self.is_goal:                                     # _flatten_observation (env.py:267-270)
+                if self.pixels_flat is not None:
+                    return {"observation": self.pixels_flat, "achieved_goal": self.achieved_goal,
+                            "desired_goal": self.desired_goal}
                 flat = self.pixels.reshape(self.num_envs, -1).to(_torch().float32).div_(255.0)
                 return {"observation": _torch().cat([flat, agent_pos], dim=1), "achieved_goal": self.achieved_goal,
                         "desired_goal": self.desired_goal}

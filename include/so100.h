@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SO100_ABI_VERSION 18  /* 18: env packing of the fused step (so100_set_env_packing, so100_env_packing, so100_env_order, so100_env_cost, so100_wave_cost);  17: so100_pool_stats (the fused step's contact-record pool, sized never to run out);  16: so100_source_hash;  15: the EE variant's mocap marker box collides (SO100_NGEOM 16, SO100_NPAIR 209, SO100_NCON_MAX 643, debug stride 3,922);  14: no per-env contact cap (SO100_NCON_MAX: every pair at its collider's maximum), debug stride 3,436 (SO100_DBG_OVF), ncon_dropped always 0, status -3 for a caught C++ exception;  13: so100_buffers.ep_return / ep_final / ep_accum (device-side episode statistics);  12: so100_model.convex (GJK/EPA mesh collider, MuJoCo 3.3.3 default), box-box up to 8 contacts, cube-table one convex contact;  11: so100_buffers.ncon_dropped, debug stride 160 (contact friction forces), so100_set_fused_build;  10: so100_hull_cells (MPR support lookup);  9: pad/link-hull pairs (SO100_NPAIR 191);  8: fused step kernel, so100_set_step_mode;  7: reward64 buffer;  6: Base hull + pad pairs (SO100_NPAIR 155, SO100_NHULL_ALL 10); 5: EE/mocap weld, render API */
+#define SO100_ABI_VERSION 19  /* 19: so100_render_to / so100_image_out (one render launch, several sinks: hwc, chw, flat float32);  18: env packing of the fused step (so100_set_env_packing, so100_env_packing, so100_env_order, so100_env_cost, so100_wave_cost);  17: so100_pool_stats (the fused step's contact-record pool, sized never to run out);  16: so100_source_hash;  15: the EE variant's mocap marker box collides (SO100_NGEOM 16, SO100_NPAIR 209, SO100_NCON_MAX 643, debug stride 3,922);  14: no per-env contact cap (SO100_NCON_MAX: every pair at its collider's maximum), debug stride 3,436 (SO100_DBG_OVF), ncon_dropped always 0, status -3 for a caught C++ exception;  13: so100_buffers.ep_return / ep_final / ep_accum (device-side episode statistics);  12: so100_model.convex (GJK/EPA mesh collider, MuJoCo 3.3.3 default), box-box up to 8 contacts, cube-table one convex contact;  11: so100_buffers.ncon_dropped, debug stride 160 (contact friction forces), so100_set_fused_build;  10: so100_hull_cells (MPR support lookup);  9: pad/link-hull pairs (SO100_NPAIR 191);  8: fused step kernel, so100_set_step_mode;  7: reward64 buffer;  6: Base hull + pad pairs (SO100_NPAIR 155, SO100_NHULL_ALL 10); 5: EE/mocap weld, render API */
 
 /* tasks (gym_so100/__init__.py:4-32 ids; single_arm.py task classes) */
 #define SO100_TASK_CUBE_TO_BIN 0          /* gym_so100/SO100CubeToBin-v0, TimeLimit 700 */
@@ -231,6 +231,21 @@ int so100_render_mesh(so100_env* env, const float* tri, const int* body, const f
  * Enqueued on stream; width <= 4096 and width * height <= 1 << 22. */
 int so100_render(so100_env* env, const float* qpos, const uint8_t* mask, const so100_camera* cam, int width,
                  int height, uint8_t* out, void* stream);
+/* (ABI 19) The same launch with several sinks: the image is rasterised once and the band -> image phase writes every
+ * non-NULL sink.  A masked-out env is untouched in every sink; background is 0 / 0.0f.  No alignment is asked of any
+ * pointer: a sink may be a slice of a larger allocation. */
+typedef struct so100_image_out {
+  uint32_t size;        /* sizeof(so100_image_out): the callee rejects a mismatch */
+  uint8_t* hwc;         /* [n][H][W][3] or NULL (what so100_render writes) */
+  uint8_t* chw;         /* [n][3][H][W] or NULL */
+  float*   flat;        /* [n][flat_pitch] or NULL: floats [0, 3HW) of env i = its HWC bytes / 255, each quotient the
+                           true float32 division (numpy's np.float32(b) / np.float32(255), the reference's env.py:267-270) */
+  int64_t  flat_pitch;  /* floats per env, >= 3*H*W; floats beyond 3HW are never written */
+} so100_image_out;
+/* Nonzero (text in so100_last_error) for a NULL env, a wrong `size`, no sink at all or flat_pitch < 3HW, and for what
+ * so100_render rejects.  so100_render is the hwc-only case of this call. */
+int so100_render_to(so100_env* env, const float* qpos, const uint8_t* mask, const so100_camera* cam, int width,
+                    int height, const so100_image_out* out, void* stream);
 
 /* Batched sparse GoalEnv reward (env.py:341-353): out[i] = ||a_i - d_i|| < threshold ? 0 : -1. */
 int so100_goal_reward(so100_env* env, int n, const float* achieved, const float* desired, float* out,
