@@ -29,6 +29,11 @@ hipError_t launch_contact_count(const Workspace&, int, uint64_t*, hipStream_t);
 hipError_t launch_contact_counts(const Workspace&, int, int32_t*, hipStream_t);
 hipError_t launch_render(const DevModel*, const float4*, const int*, const uint32_t*, int, const float*,
                          const uint8_t*, const so100_camera&, int, int, int, const so100_image_out&, hipStream_t);
+hipError_t launch_render_views(const DevModel*, const float4*, const int*, const uint8_t*, int, const float*,
+                               const uint8_t*, const so100_camera&, const so100_view*, int, int, int,
+                               const so100_image_out&, hipStream_t);
+hipError_t launch_views_sample(const so100_view_dr&, const so100_camera&, const uint32_t*, const uint32_t*,
+                               const uint8_t*, so100_view*, int, int, hipStream_t);
 hipError_t alloc_workspace(int, Workspace*);
 hipError_t alloc_fused_workspace(int, Workspace*);
 hipError_t free_workspace(Workspace*);
@@ -84,6 +89,7 @@ struct so100_env {
   int* r_body = nullptr;
   uint32_t* r_rgb = nullptr;
   int r_ntri = 0;
+  uint8_t* r_mat = nullptr;     // per-triangle material ids of that mesh (so100_render_materials), or none yet
   // profiling (so100_profile_enable): events[step][prof_per] (2 nsubstep + 2 split, 2 fused)
   std::vector<hipEvent_t> prof_ev;
   int prof_cap = 0, prof_used = 0, prof_per = 0;
@@ -783,6 +789,7 @@ static int so100_destroy_impl(so100_env* env) {
   if (env->r_tri) (void)hipFree(env->r_tri);
   if (env->r_body) (void)hipFree(env->r_body);
   if (env->r_rgb) (void)hipFree(env->r_rgb);
+  if (env->r_mat) (void)hipFree(env->r_mat);
   hipError_t e = hipFree(env->d_model);
   if (env->d_cand) (void)hipFree(env->d_cand);
   hipError_t e2 = free_chunks(env);
@@ -1176,7 +1183,8 @@ static int so100_render_mesh_impl(so100_env* env, const float* tri, const int* b
   if (env->r_tri) (void)hipFree(env->r_tri);
   if (env->r_body) (void)hipFree(env->r_body);
   if (env->r_rgb) (void)hipFree(env->r_rgb);
-  env->r_tri = nullptr; env->r_body = nullptr; env->r_rgb = nullptr; env->r_ntri = 0;
+  if (env->r_mat) (void)hipFree(env->r_mat);
+  env->r_tri = nullptr; env->r_body = nullptr; env->r_rgb = nullptr; env->r_mat = nullptr; env->r_ntri = 0;
   hipError_t e = hipMalloc(&env->r_tri, t.size() * sizeof(float4));
   if (e == hipSuccess) e = hipMalloc(&env->r_body, (size_t)ntri * sizeof(int));
   if (e == hipSuccess) e = hipMalloc(&env->r_rgb, (size_t)ntri * sizeof(uint32_t));
@@ -1188,9 +1196,11 @@ static int so100_render_mesh_impl(so100_env* env, const float* tri, const int* b
   return 0;
 }
 
-// the one render launch behind so100_render (hwc alone) and so100_render_to; `who` names the entry point in errors
+// the one render launch behind so100_render (hwc alone), so100_render_to and, with a record per env (views != nullptr),
+// so100_render_views; `who` names the entry point in errors
 static int render_launch(const char* who, so100_env* env, const float* qpos, const uint8_t* mask, const so100_camera* cam,
-                         int width, int height, const so100_image_out& o, void* stream) {
+                         int width, int height, const so100_image_out& o, void* stream,
+                         const so100_view* views = nullptr) {
   char msg[160];
   auto bad = [&](const char* what) {
     snprintf(msg, sizeof(msg), "%s: %s", who, what);
@@ -1204,9 +1214,12 @@ static int render_launch(const char* who, so100_env* env, const float* qpos, con
   if (o.flat && o.flat_pitch < (int64_t)3 * width * height) return bad("flat_pitch < 3*H*W");
   if (cam->nlight < 0 || cam->nlight > SO100_MAX_LIGHTS || !(cam->fovy > 0.f && cam->fovy < 180.f))
     return bad("bad camera");
+  if (views && !env->r_mat) return bad("no materials (so100_render_materials)");
   DeviceGuard g(env->device);
-  hipError_t e = so100::launch_render(env->d_model, env->r_tri, env->r_body, env->r_rgb, env->r_ntri, qpos, mask, *cam,
-                                      env->n, width, height, o, (hipStream_t)stream);
+  hipError_t e = views ? so100::launch_render_views(env->d_model, env->r_tri, env->r_body, env->r_mat, env->r_ntri, qpos,
+                                                    mask, *cam, views, env->n, width, height, o, (hipStream_t)stream)
+                       : so100::launch_render(env->d_model, env->r_tri, env->r_body, env->r_rgb, env->r_ntri, qpos, mask,
+                                              *cam, env->n, width, height, o, (hipStream_t)stream);
   return e == hipSuccess ? 0 : fail_hip(who, e);
 }
 
@@ -1231,8 +1244,96 @@ static int so100_render_to_impl(so100_env* env, const float* qpos, const uint8_t
   return render_launch("so100_render_to", env, qpos, mask, cam, width, height, *out, stream);
 }
 
+// the size check of a caller-filled struct: nothing else of it is read before it is known to be this library's layout
+static int size_mismatch(const char* who, const char* what, uint32_t got, size_t want) {
+  char msg[160];
+  snprintf(msg, sizeof(msg), "%s: %s.size %u, expected %zu", who, what, got, want);
+  return fail(msg);
+}
+
+static int so100_render_materials_impl(so100_env* env, const uint8_t* material, int ntri) {
+  if (!env || !material) return fail("so100_render_materials: bad arguments");
+  if (env->r_ntri <= 0) return fail("so100_render_materials: no render mesh (so100_render_mesh)");
+  if (ntri != env->r_ntri) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "so100_render_materials: ntri %d, the mesh has %d", ntri, env->r_ntri);
+    return fail(msg);
+  }
+  for (int i = 0; i < ntri; i++)
+    if (material[i] >= SO100_NMATERIAL) return fail("so100_render_materials: material id out of range");
+  DeviceGuard g(env->device);
+  hipError_t e = hipSuccess;
+  if (!env->r_mat) e = hipMalloc(&env->r_mat, (size_t)ntri);
+  if (e == hipSuccess) e = hipMemcpy(env->r_mat, material, (size_t)ntri, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (env->r_mat) (void)hipFree(env->r_mat);
+    env->r_mat = nullptr;
+    return fail_hip("so100_render_materials", e);
+  }
+  return 0;
+}
+
+static int so100_render_views_impl(so100_env* env, const float* qpos, const uint8_t* mask, const so100_camera* cam,
+                                   const so100_view* views, int width, int height, const so100_image_out* out,
+                                   void* stream) {
+  if (!out) return fail("so100_render_views: NULL out");
+  if (out->size != sizeof(so100_image_out))
+    return size_mismatch("so100_render_views", "so100_image_out", out->size, sizeof(so100_image_out));
+  if (!env) return fail("so100_render_views: NULL env");
+  if (!views) return fail("so100_render_views: NULL views");
+  return render_launch("so100_render_views", env, qpos, mask, cam, width, height, *out, stream, views);
+}
+
+static int so100_views_sample_impl(so100_env* env, const so100_view_dr* dr, const so100_camera* cam,
+                                   const uint32_t* base_rgb, const uint32_t* episode, const uint8_t* mask,
+                                   so100_view* views, void* stream) {
+  if (!dr) return fail("so100_views_sample: NULL dr");
+  if (dr->size != sizeof(so100_view_dr))
+    return size_mismatch("so100_views_sample", "so100_view_dr", dr->size, sizeof(so100_view_dr));
+  if (!env) return fail("so100_views_sample: NULL env");
+  if (!cam || !base_rgb || !views) return fail("so100_views_sample: NULL cam, base_rgb or views");
+  auto pair_ok = [](const float* r) { return r[0] >= 0.f && r[1] >= r[0]; };     // false for NaN
+  bool ok = dr->cam_pos >= 0.f && dr->cam_rot >= 0.f && dr->light_rot >= 0.f && pair_ok(dr->fovy) &&
+            pair_ok(dr->ambient) && pair_ok(dr->headlight);
+  for (int l = 0; l < SO100_MAX_LIGHTS; l++) ok = ok && pair_ok(dr->light[l]);
+  for (int m = 0; m < SO100_NMATERIAL; m++) ok = ok && pair_ok(dr->color[m]);
+  if (!ok) return fail("so100_views_sample: bad range (half-widths >= 0, 0 <= lo <= hi)");
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_views_sample(*dr, *cam, base_rgb, episode, mask, views, env->n, env->env_offset,
+                                            (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip("so100_views_sample", e);
+}
+
 
 extern "C" {
+
+int so100_view_bytes(void) { return (int)sizeof(so100_view); }
+
+int so100_render_materials(so100_env* env, const uint8_t* material, int ntri) {
+  try {
+    return so100_render_materials_impl(env, material, ntri);
+  } catch (...) {
+    return caught("so100_render_materials");
+  }
+}
+
+int so100_render_views(so100_env* env, const float* qpos, const uint8_t* mask, const so100_camera* cam,
+                       const so100_view* views, int width, int height, const so100_image_out* out, void* stream) {
+  try {
+    return so100_render_views_impl(env, qpos, mask, cam, views, width, height, out, stream);
+  } catch (...) {
+    return caught("so100_render_views");
+  }
+}
+
+int so100_views_sample(so100_env* env, const so100_view_dr* dr, const so100_camera* cam, const uint32_t* base_rgb,
+                       const uint32_t* episode, const uint8_t* mask, so100_view* views, void* stream) {
+  try {
+    return so100_views_sample_impl(env, dr, cam, base_rgb, episode, mask, views, stream);
+  } catch (...) {
+    return caught("so100_views_sample");
+  }
+}
 
 int so100_abi_version(void) {
   try {

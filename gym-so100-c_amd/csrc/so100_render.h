@@ -1,9 +1,11 @@
-// so100_render.h - the render kernel's body, shared by its two launches: so100_render.hip (the hwc image alone) and
-// so100_render_sinks.hip (so100_render_to's further sinks).  One translation unit per kernel: with both instantiations
-// in one unit the hwc-only kernel was scheduled differently and measured slower.
+// so100_render.h - the render kernel's body, shared by its three launches: so100_render.hip (the hwc image alone),
+// so100_render_sinks.hip (so100_render_to's further sinks) and so100_render_views.hip (so100_render_views: camera,
+// lights and colours per env).  One translation unit per kernel: with two instantiations in one unit the hwc-only
+// kernel was scheduled differently and measured slower.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "so100_device.h"
 #include "so100.h"
 #include "so100_common.h"
@@ -35,6 +37,19 @@ struct RenderSinkArgs : RenderArgs {
   float* flat;                          // [n][flat_pitch] or null: floats [0, 3HW) = the hwc bytes / 255
   long long flat_pitch;
 };
+// the launch with a view record per env (so100_render_views): pos, mat, fovy, the headlight terms, the light directions
+// and diffuses and the five base colours come from views[env]; a.cam keeps the launch-uniform track, znear and nlight
+struct RenderViewArgs : RenderSinkArgs {
+  const so100_view* views;              // [n]
+  const uint8_t* material;              // [ntri] material id < SO100_NMATERIAL: the base colour is views[env].rgb[id]
+};
+constexpr int kViewWords = (int)(sizeof(so100_view) / sizeof(uint32_t));
+static_assert(sizeof(so100_view) == 160 && kViewWords == 40, "so100_view: 40 dwords");
+// the env's record in LDS, filled one dword per thread
+union ViewLds {
+  so100_view v;
+  uint32_t w[kViewWords];
+};
 
 // byte / 255 as numpy divides it (np.float32(b) / np.float32(255), the reference's env.py:267-270): the quotients are
 // rounded by the compiler's IEEE constant evaluation, never by a reciprocal multiply on the device
@@ -45,7 +60,9 @@ struct ByteUnit {
   }
 };
 
-DEV uint32_t shade(const RenderArgs& a, const float* cm, const float* p0, const float* p1, const float* p2,
+// c: where pos, the headlight terms and the lights come from: the launch's so100_camera or the env's so100_view
+template <class Cam>
+DEV uint32_t shade(const Cam& c, int nlight, const float* cm, const float* p0, const float* p1, const float* p2,
                    uint32_t rgb) {
   float e1[3], e2[3], nrm[3];
 #pragma unroll
@@ -56,27 +73,37 @@ DEV uint32_t shade(const RenderArgs& a, const float* cm, const float* p0, const 
 #pragma unroll
   for (int k = 0; k < 3; k++) nrm[k] *= inv;
   // two-sided: the normal facing the camera
-  float v[3] = {a.cam.pos[0] - p0[0], a.cam.pos[1] - p0[1], a.cam.pos[2] - p0[2]};
+  float v[3] = {c.pos[0] - p0[0], c.pos[1] - p0[1], c.pos[2] - p0[2]};
   if (dot3(nrm, v) < 0.f) { nrm[0] = -nrm[0]; nrm[1] = -nrm[1]; nrm[2] = -nrm[2]; }
   // headlight: along the view direction (camera -z), so its diffuse term is n . z_cam
   const float zc[3] = {cm[2], cm[5], cm[8]};
-  float lum = a.cam.head_ambient + a.cam.head_diffuse * fmaxf(0.f, dot3(nrm, zc));
-  for (int l = 0; l < a.cam.nlight; l++) lum += a.cam.light_diffuse[l] * fmaxf(0.f, -dot3(nrm, a.cam.light_dir[l]));
+  float lum = c.head_ambient + c.head_diffuse * fmaxf(0.f, dot3(nrm, zc));
+  for (int l = 0; l < nlight; l++) lum += c.light_diffuse[l] * fmaxf(0.f, -dot3(nrm, c.light_dir[l]));
   uint32_t out = 0;
 #pragma unroll
-  for (int c = 0; c < 3; c++) {
-    const float base = (float)((rgb >> (8 * c)) & 0xFFu) * (1.f / 255.f);
+  for (int k = 0; k < 3; k++) {
+    const float base = (float)((rgb >> (8 * k)) & 0xFFu) * (1.f / 255.f);
     const float val = fminf(fmaxf(base * lum, 0.f), 1.f);
-    out |= (uint32_t)(val * 255.f + 0.5f) << (8 * c);
+    out |= (uint32_t)(val * 255.f + 0.5f) << (8 * k);
   }
   return out;
 }
 
+// the camera-like record the body reads: a.cam, or with views the env's record in LDS
+template <class Args>
+DEV decltype(auto) view_source(const Args& a, const ViewLds& vl) {
+  if constexpr (std::is_same<Args, RenderViewArgs>::value) return (vl.v);
+  else return (a.cam);
+}
+
 // Args = RenderArgs: the hwc image alone (so100_render and every hwc-only so100_render_to);
-// Args = RenderSinkArgs: every non-null sink of a.out / a.chw / a.flat is written from the same band.
+// Args = RenderSinkArgs: every non-null sink of a.out / a.chw / a.flat is written from the same band;
+// Args = RenderViewArgs: the same sinks, drawn from views[env] (not referenced, vl costs the other two no LDS).
 template <class Args>
 __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
   constexpr bool kSinks = sizeof(Args) != sizeof(RenderArgs);
+  constexpr bool kView = std::is_same<Args, RenderViewArgs>::value;
+  __shared__ ViewLds vl;
   __shared__ EnvShared sh;
   __shared__ float frm[SO100_NBODY][12];           // body rotation (9) + position (3)
   __shared__ unsigned long long zb[kTilePx];
@@ -90,6 +117,10 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
 
   // ---- forward kinematics of this env (the stage kernel's fk_stage on thread 0)
   if (tid < SO100_NQ) sh.qpos[tid] = a.qpos[(size_t)env * SO100_NQ + tid];
+  if constexpr (kView) {
+    if (tid < kViewWords) vl.w[tid] = reinterpret_cast<const uint32_t*>(a.views + env)[tid];
+  }
+  const auto& cv = view_source(a, vl);                     // read after the barrier below
   __syncthreads();
   joint_sincos(sh, tid);
   __syncthreads();
@@ -115,7 +146,7 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
     if (a.cam.track) {
       // mode="targetbody" on the ee body (scene_so100.xml:30 front_close -> vx300s_left/camera_focus, whose
       // origin is ee_site): MuJoCo's mj_camlight frame z = pos - target, x = (0,0,1) x z, y = z x x
-      float z[3] = {a.cam.pos[0] - sh.site_ee[0], a.cam.pos[1] - sh.site_ee[1], a.cam.pos[2] - sh.site_ee[2]};
+      float z[3] = {cv.pos[0] - sh.site_ee[0], cv.pos[1] - sh.site_ee[1], cv.pos[2] - sh.site_ee[2]};
       float x[3], y[3];
       const float up[3] = {0.f, 0.f, 1.f};
       float n = sqrtf(dot3(z, z));
@@ -126,12 +157,12 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
       cross3(y, z, x);
       for (int k = 0; k < 3; k++) { cmat[3 * k] = x[k]; cmat[3 * k + 1] = y[k]; cmat[3 * k + 2] = z[k]; }
     } else {
-      for (int k = 0; k < 9; k++) cmat[k] = a.cam.mat[k];
+      for (int k = 0; k < 9; k++) cmat[k] = cv.mat[k];
     }
   }
   __syncthreads();
 
-  const float th = tanf(0.5f * a.cam.fovy * 0.017453292519943295f);
+  const float th = tanf(0.5f * cv.fovy * 0.017453292519943295f);
   const float aspect = (float)W / (float)H;
   const int band = kTilePx / W > 0 ? kTilePx / W : 1;        // rows per band
   uint8_t* img = a.out + (size_t)env * H * W * 3;              // used where a.out is not null
@@ -157,7 +188,7 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
         w[0] = R[0] * q.x + R[1] * q.y + R[2] * q.z + R[9];
         w[1] = R[3] * q.x + R[4] * q.y + R[5] * q.z + R[10];
         w[2] = R[6] * q.x + R[7] * q.y + R[8] * q.z + R[11];
-        const float d[3] = {w[0] - a.cam.pos[0], w[1] - a.cam.pos[1], w[2] - a.cam.pos[2]};
+        const float d[3] = {w[0] - cv.pos[0], w[1] - cv.pos[1], w[2] - cv.pos[2]};
         const float cx = cmat[0] * d[0] + cmat[3] * d[1] + cmat[6] * d[2];
         const float cy = cmat[1] * d[0] + cmat[4] * d[1] + cmat[7] * d[2];
         const float cz = cmat[2] * d[0] + cmat[5] * d[1] + cmat[8] * d[2];
@@ -178,7 +209,10 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
       by0 = max(y0, (int)floorf(fminf(sy[0], fminf(sy[1], sy[2])) - 0.5f));
       by1 = min(y1 - 1, (int)ceilf(fmaxf(sy[0], fmaxf(sy[1], sy[2])) - 0.5f));
       if (bx0 > bx1 || by0 > by1) return false;
-      col = shade(a, cmat, pw[0], pw[1], pw[2], a.tri_rgb[t]);
+      uint32_t base;
+      if constexpr (kView) base = cv.rgb[a.material[t]];
+      else base = a.tri_rgb[t];
+      col = shade(cv, a.cam.nlight, cmat, pw[0], pw[1], pw[2], base);
       return true;
     };
     // one pixel of a set-up triangle: edge functions at the pixel centre, perspective-correct depth

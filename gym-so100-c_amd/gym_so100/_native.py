@@ -48,6 +48,40 @@ class SO100ImageOut(ctypes.Structure):
         super().__init__(ctypes.sizeof(SO100ImageOut), hwc, chw, flat, flat_pitch)
 
 
+SO100_NMATERIAL = 5
+
+
+class SO100View(ctypes.Structure):
+    """Mirror of ``so100_view`` (include/so100.h): one env's camera pose, field of view, lights and the five materials'
+    base colours for ``so100_render_views``; 40 dwords, device memory ([N, 40] int32 / float32 tensors)."""
+    _fields_ = [("pos", ctypes.c_float * 3), ("mat", ctypes.c_float * 9), ("fovy", ctypes.c_float),
+                ("head_ambient", ctypes.c_float), ("head_diffuse", ctypes.c_float),
+                ("light_diffuse", ctypes.c_float * SO100_MAX_LIGHTS),
+                ("light_dir", (ctypes.c_float * 3) * SO100_MAX_LIGHTS), ("rgb", ctypes.c_uint32 * SO100_NMATERIAL),
+                ("reserved", ctypes.c_uint32 * 4)]
+
+
+VIEW_WORDS = ctypes.sizeof(SO100View) // 4
+
+
+class SO100ViewDR(ctypes.Structure):
+    """Mirror of ``so100_view_dr`` (include/so100.h): the ranges ``so100_views_sample`` draws the records from.  The
+    default is every range at zero width (the base view); ``size`` is set to the mirror's size, which the callee checks
+    against its own."""
+    _fields_ = [("size", ctypes.c_uint32), ("reserved0", ctypes.c_uint32), ("seed", ctypes.c_uint64),
+                ("cam_pos", ctypes.c_float), ("cam_rot", ctypes.c_float), ("fovy", ctypes.c_float * 2),
+                ("ambient", ctypes.c_float * 2), ("headlight", ctypes.c_float * 2),
+                ("light", (ctypes.c_float * 2) * SO100_MAX_LIGHTS), ("light_rot", ctypes.c_float),
+                ("color", (ctypes.c_float * 2) * SO100_NMATERIAL), ("reserved1", ctypes.c_float)]
+
+    def __init__(self, seed=0):
+        super().__init__()
+        self.size = ctypes.sizeof(SO100ViewDR)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        for pair in (self.fovy, self.ambient, self.headlight, *self.light, *self.color):
+            pair[0] = pair[1] = 1.0
+
+
 class NativeLibraryError(RuntimeError):
     pass
 
@@ -55,7 +89,7 @@ class NativeLibraryError(RuntimeError):
 _lib = None
 
 
-ABI_VERSION = 19         # include/so100.h SO100_ABI_VERSION
+ABI_VERSION = 20         # include/so100.h SO100_ABI_VERSION
 HULL_CELLG = 8           # SO100_HULL_CELLG
 HULL_NCELL = 6 * HULL_CELLG * HULL_CELLG
 
@@ -96,6 +130,11 @@ def load():
     lib.so100_render.argtypes = [_P, _P, _P, ctypes.POINTER(SO100Camera), ctypes.c_int, ctypes.c_int, _P, _P]
     lib.so100_render_to.argtypes = [_P, _P, _P, ctypes.POINTER(SO100Camera), ctypes.c_int, ctypes.c_int,
                                     ctypes.POINTER(SO100ImageOut), _P]
+    lib.so100_view_bytes.argtypes = []
+    lib.so100_render_materials.argtypes = [_P, _P, ctypes.c_int]
+    lib.so100_render_views.argtypes = [_P, _P, _P, ctypes.POINTER(SO100Camera), _P, ctypes.c_int, ctypes.c_int,
+                                       ctypes.POINTER(SO100ImageOut), _P]
+    lib.so100_views_sample.argtypes = [_P, ctypes.POINTER(SO100ViewDR), ctypes.POINTER(SO100Camera), _P, _P, _P, _P, _P]
     lib.so100_hull_cells.argtypes = [_P, _P, _P, ctypes.c_int]
     lib.so100_set_fused_build.argtypes = [_P, ctypes.c_int]
     lib.so100_fused_build.argtypes = [_P, ctypes.c_int]
@@ -109,7 +148,8 @@ def load():
                "so100_profile_enable", "so100_profile_read", "so100_contact_count", "so100_contact_counts",
                "so100_pool_stats", "so100_chunk_info", "so100_render_mesh", "so100_render", "so100_render_to", "so100_set_step_mode", "so100_step_mode", "so100_hull_cells",
                "so100_set_fused_build", "so100_fused_build", "so100_set_env_packing", "so100_env_packing",
-               "so100_env_order", "so100_env_cost", "so100_wave_cost"):
+               "so100_env_order", "so100_env_cost", "so100_wave_cost", "so100_view_bytes", "so100_render_materials",
+               "so100_render_views", "so100_views_sample"):
         getattr(lib, fn).restype = ctypes.c_int
     lib.so100_struct_sizes.argtypes = [_P, _P]
     lib.so100_struct_sizes.restype = ctypes.c_int
@@ -121,6 +161,9 @@ def load():
     if mb.value != ctypes.sizeof(SO100Model) or bb.value != ctypes.sizeof(SO100Buffers):
         raise NativeLibraryError(f"struct layout mismatch: so100_model {mb.value} vs {ctypes.sizeof(SO100Model)}, "
                                  f"so100_buffers {bb.value} vs {ctypes.sizeof(SO100Buffers)}")
+    if lib.so100_view_bytes() != ctypes.sizeof(SO100View):
+        raise NativeLibraryError(f"struct layout mismatch: so100_view {lib.so100_view_bytes()} vs "
+                                 f"{ctypes.sizeof(SO100View)}")
     _lib = lib
     return lib
 
@@ -132,7 +175,8 @@ EXPORTED_SYMBOLS = ("so100_abi_version", "so100_last_error", "so100_source_hash"
                     "so100_render", "so100_render_to",
                     "so100_set_step_mode", "so100_step_mode", "so100_hull_cells", "so100_set_fused_build",
                     "so100_fused_build", "so100_set_env_packing", "so100_env_packing", "so100_env_order",
-                    "so100_env_cost", "so100_wave_cost")
+                    "so100_env_cost", "so100_wave_cost", "so100_view_bytes", "so100_render_materials",
+                    "so100_render_views", "so100_views_sample")
 
 
 def source_hash():

@@ -9,6 +9,10 @@ fovy 78 and the scene's headlight + three directional lights.  Output: uint8 [N,
 ``channels_first`` [N, 3, H, W]; ``render(flat=...)`` also fills a float32 [N, >= 3HW] tensor with the image / 255
 in the same launch (C-ABI ``so100_render_to``: one rasterisation, several sinks).
 
+Visual domain randomisation: with ``CameraRenderer.views`` set (a device [N, 40] tensor of ``so100_view`` records,
+``identity_views`` / ``sample_views``) env i is drawn from its own camera pose, field of view, lights and material
+colours (C-ABI ``so100_render_views``); without it every env is drawn from the one camera, as before.
+
 It is a rasteriser of its own, not MuJoCo's OpenGL pipeline: geometry and colours are the scene's, the
 pixel values are not MuJoCo's (no specular, shadows, fog or anti-aliasing).
 """
@@ -23,6 +27,10 @@ ASSET = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets", "so10
 CAMERAS = ("top", "angle", "left_pillar", "right_pillar", "front_close")
 TRACKING = ("front_close",)              # mode="targetbody" on the ee body: frame per env
 ZNEAR = 0.01
+MATERIALS = ("table", "bin", "arm_light", "arm_dark", "cube")      # SO100_NMATERIAL ids 0..4 (include/so100.h)
+# the keys of a visual-randomisation dict (SO100VecEnv.set_domain_randomization(visual=...), sample_views(ranges))
+VISUAL_KEYS = ("camera_pos", "camera_rot_deg", "fovy", "ambient", "headlight", "lights", "light_rot_deg", "colors",
+               "per_episode", "seed")
 
 
 def _torch():
@@ -56,6 +64,87 @@ def make_camera(scene, name="top"):
     return cam
 
 
+def material_ids(scene):
+    """(ids uint8 [ntri], base float32 [5, 3]): each triangle's material and each material's one base colour, from the
+    asset's (body, rgb): body 0 grey 0.2 is the table and grey 0.5 the bin, bodies 1-7 at 1.0 are the arm's light parts
+    and at 0.1 its dark parts, body 8 is the cube.  ValueError for a triangle that fits no material and for a material
+    with more than one base colour."""
+    body = np.asarray(scene["body"])
+    rgb = np.asarray(scene["rgb"], dtype=np.float32)
+    grey = (rgb[:, 0] == rgb[:, 1]) & (rgb[:, 1] == rgb[:, 2])
+
+    def is_grey(v):
+        return grey & (rgb[:, 0] == np.float32(v))
+    arm = (body >= 1) & (body <= 7)
+    which = [(body == 0) & is_grey(0.2), (body == 0) & is_grey(0.5), arm & is_grey(1.0), arm & is_grey(0.1), body == 8]
+    count = np.sum(which, axis=0)
+    if np.any(count != 1):
+        raise ValueError(f"{int(np.sum(count != 1))} triangles fit no material of {MATERIALS} (or more than one), "
+                         f"the first: triangle {int(np.nonzero(count != 1)[0][0])}")
+    ids = np.zeros(len(body), dtype=np.uint8)
+    base = np.zeros((len(MATERIALS), 3), dtype=np.float32)
+    for k, w in enumerate(which):
+        ids[w] = k
+        cols = np.unique(rgb[w], axis=0)
+        if len(cols) > 1:
+            raise ValueError(f"material {MATERIALS[k]!r} has {len(cols)} base colours")
+        if len(cols):
+            base[k] = cols[0]
+    return ids, base
+
+
+def pack_rgb8(rgb):
+    """float32 [..., 3] in [0, 1] -> packed RGB8 as so100_render_mesh packs tri_rgb (float32 x * 255 + 0.5, truncated)"""
+    x = np.clip(np.asarray(rgb, dtype=np.float32), np.float32(0), np.float32(1))
+    q = (x * np.float32(255) + np.float32(0.5)).astype(np.uint32)
+    return q[..., 0] | (q[..., 1] << 8) | (q[..., 2] << 16)
+
+
+def _pair(v, what):
+    lo, hi = (float(x) for x in v)
+    if not 0.0 <= lo <= hi:
+        raise ValueError(f"{what}: a scale range (lo, hi) with 0 <= lo <= hi, got {v!r}")
+    return lo, hi
+
+
+def view_ranges(ranges, seed):
+    """so100_view_dr from a visual-randomisation dict (keys VISUAL_KEYS; a missing key leaves that part at its base):
+    camera_pos: half-width in metres; camera_rot_deg, light_rot_deg: half-widths in degrees of a rotation vector's
+    components; fovy, ambient, headlight: (lo, hi) scales; lights: one (lo, hi) for every directional light or a list
+    of one per light; colors: one (lo, hi) or a dict by material name (MATERIALS)."""
+    unknown = set(ranges) - set(VISUAL_KEYS)
+    if unknown:
+        raise ValueError(f"visual randomisation: unknown keys {sorted(unknown)}; known: {VISUAL_KEYS}")
+    dr = _native.SO100ViewDR(seed)
+    for key, field in (("camera_pos", "cam_pos"), ("camera_rot_deg", "cam_rot"), ("light_rot_deg", "light_rot")):
+        hw = float(ranges.get(key, 0.0))
+        if not hw >= 0.0:
+            raise ValueError(f"{key}: a half-width >= 0, got {hw!r}")
+        setattr(dr, field, float(np.radians(hw)) if key.endswith("_deg") else hw)
+    for key in ("fovy", "ambient", "headlight"):
+        if key in ranges:
+            getattr(dr, key)[:] = _pair(ranges[key], key)
+    if "lights" in ranges:
+        li = ranges["lights"]
+        per = [li] * _native.SO100_MAX_LIGHTS if np.ndim(li) == 1 else list(li)
+        if len(per) > _native.SO100_MAX_LIGHTS:
+            raise ValueError("lights: more ranges than SO100_MAX_LIGHTS")
+        for k, v in enumerate(per):
+            dr.light[k][:] = _pair(v, "lights")
+    if "colors" in ranges:
+        co = ranges["colors"]
+        if isinstance(co, dict):
+            bad = set(co) - set(MATERIALS)
+            if bad:
+                raise ValueError(f"colors: unknown materials {sorted(bad)}; known: {MATERIALS}")
+            co = {MATERIALS.index(k): v for k, v in co.items()}
+        else:
+            co = {k: co for k in range(len(MATERIALS))}
+        for k, v in co.items():
+            dr.color[k][:] = _pair(v, "colors")
+    return dr
+
+
 class CameraRenderer:
     """Renders every env of ``venv`` (an SO100VecEnv) from one camera into a persistent uint8 tensor.
 
@@ -75,6 +164,12 @@ class CameraRenderer:
         rgb = np.ascontiguousarray(scene["rgb"], dtype=np.float32)
         _native.check(venv.lib.so100_render_mesh(venv._handle, tri.ctypes.data, body.ctypes.data, rgb.ctypes.data,
                                                  len(body)), "so100_render_mesh")
+        # the material ids belong to the mesh (a new mesh drops them): uploaded with it, read only by render_views
+        mat, base = material_ids(scene)
+        _native.check(venv.lib.so100_render_materials(venv._handle, mat.ctypes.data, len(mat)),
+                      "so100_render_materials")
+        self.base_rgb = np.ascontiguousarray(pack_rgb8(base), dtype=np.uint32)       # [5] packed RGB8 per material
+        self.views = None                # [N, 40] int32 device tensor of so100_view records, or None: one camera
         self.camera_name = camera
         self.camera = make_camera(scene, camera)
         self.ntri = len(body)
@@ -82,13 +177,46 @@ class CameraRenderer:
         self.image_shape = (3, self.height, self.width) if self.channels_first else (self.height, self.width, 3)
         self.pixels = torch.zeros(venv.num_envs, *self.image_shape, dtype=torch.uint8, device=venv.device)
 
-    def render(self, qpos=None, out=None, mask=None, flat=None):
+    def identity_views(self):
+        """Set ``views`` to the base view in every env (the renderer's camera, the scene's lights and colours): the
+        images are then bit for bit those without views.  Returns the tensor."""
+        return self.sample_views({}, 0)
+
+    def sample_views(self, ranges, seed, episode=None, mask=None):
+        """Draw the view records of the envs in mask (default all; the others keep theirs) on the device (C-ABI
+        so100_views_sample): ranges is a visual-randomisation dict (view_ranges), episode an [N] int32 device tensor
+        mixed into every draw (default 0).  A record is a pure function of (seed, global env id, episode).  Allocates
+        ``views`` (zeroed) on first use and returns it."""
+        torch = _torch()
+        v = self.venv
+        dr = view_ranges(ranges, seed)
+        if episode is not None and (episode.shape != (v.num_envs,) or episode.dtype != torch.int32 or
+                                    episode.device != v.device or not episode.is_contiguous()):
+            raise ValueError("episode must be a contiguous int32 [N] tensor on the env's device")
+        m = None
+        if mask is not None:
+            if mask.shape != (v.num_envs,) or mask.device != v.device:
+                raise ValueError("mask must be an [N] tensor on the env's device")
+            m = mask.to(torch.uint8).contiguous()
+            self._view_mask_ref = m               # keep alive until the launch has run
+        if self.views is None:
+            self.views = torch.zeros(v.num_envs, _native.VIEW_WORDS, dtype=torch.int32, device=v.device)
+        _native.check(v.lib.so100_views_sample(v._handle, ctypes.byref(dr), ctypes.byref(self.camera),
+                                               self.base_rgb.ctypes.data, _native.ptr(episode), _native.ptr(m),
+                                               _native.ptr(self.views), v._stream()), "so100_views_sample")
+        return self.views
+
+    def render(self, qpos=None, out=None, mask=None, flat=None, views=None):
         """Enqueue the render of qpos (default: the env's state) into out (default self.pixels); mask: [N]
         bool/uint8 device tensor of the envs to draw (the others keep their previous image and flat row).
 
         flat: a contiguous float32 [N, P] device tensor with P >= 3HW, filled by the same launch: floats [0, 3HW)
         of row i are env i's [H,W,3] bytes / 255 (numpy's float32 division, the reference's env.py:267-270),
-        whatever the renderer's own layout; the floats beyond 3HW are left as they are."""
+        whatever the renderer's own layout; the floats beyond 3HW are left as they are.
+
+        views: an [N, 40] int32 device tensor of so100_view records (default ``self.views``); when there is one, env i
+        is drawn from record i (C-ABI so100_render_views), otherwise the calls are those of a renderer without
+        views."""
         torch = _torch()
         v = self.venv
         q = v.qpos if qpos is None else qpos
@@ -104,7 +232,11 @@ class CameraRenderer:
                 raise ValueError("mask must be an [N] tensor on the env's device")
             m = mask.to(torch.uint8).contiguous()
             self._mask_ref = m                    # keep alive until the launch has run
-        if flat is None and not self.channels_first:
+        vw = self.views if views is None else views
+        if vw is not None and (vw.shape != (v.num_envs, _native.VIEW_WORDS) or vw.element_size() != 4 or
+                               not vw.is_contiguous() or vw.device != o.device):
+            raise ValueError("views must be a contiguous 4-byte [N, 40] device tensor")
+        if flat is None and not self.channels_first and vw is None:
             _native.check(v.lib.so100_render(v._handle, _native.ptr(q), _native.ptr(m), ctypes.byref(self.camera),
                                              self.width, self.height, _native.ptr(o), v._stream()), "so100_render")
             return o
@@ -117,6 +249,11 @@ class CameraRenderer:
         sinks = _native.SO100ImageOut(hwc=None if self.channels_first else _native.ptr(o),
                                       chw=_native.ptr(o) if self.channels_first else None,
                                       flat=_native.ptr(flat), flat_pitch=pitch)
+        if vw is not None:
+            _native.check(v.lib.so100_render_views(v._handle, _native.ptr(q), _native.ptr(m), ctypes.byref(self.camera),
+                                                   _native.ptr(vw), self.width, self.height, ctypes.byref(sinks),
+                                                   v._stream()), "so100_render_views")
+            return o
         _native.check(v.lib.so100_render_to(v._handle, _native.ptr(q), _native.ptr(m), ctypes.byref(self.camera),
                                             self.width, self.height, ctypes.byref(sinks), v._stream()),
                       "so100_render_to")

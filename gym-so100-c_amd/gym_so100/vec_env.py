@@ -76,7 +76,9 @@ class SO100VecEnv:
         max_episode_steps: TimeLimit; default per task as registered by the reference.
         autoreset: reset finished envs inside the step kernel.
         domain_randomization: None or dict(mass=(lo,hi), friction=(lo,hi), action_noise=sigma):
-            per-env cube mass / friction scales (fixed per env) + Gaussian action noise.
+            per-env cube mass / friction scales (fixed per env) + Gaussian action noise.  With pixel observations
+            the dict may carry ``visual=dict(...)``: camera jitter, light and colour randomisation per env
+            (``set_domain_randomization``); ValueError with any other obs_type.
         env_offset: global index of this shard's first env (multi-GPU sharding); in-kernel seeds use
             the global env id so trajectories do not depend on the number of GPUs.
         iterations: solver iterations per substep, PGS sweeps or Newton steps (default: the model's 100,
@@ -123,6 +125,10 @@ class SO100VecEnv:
             raise ValueError("channels_first: the GoalEnv's flattened pixel observation is HWC (env.py:267-270)")
         if (channels_first or flat_pixels) and obs_type != "so100_pixels_agent_pos":
             raise ValueError("channels_first / flat_pixels need obs_type='so100_pixels_agent_pos'")
+        if domain_randomization and domain_randomization.get("visual") is not None:
+            if obs_type != "so100_pixels_agent_pos":
+                raise ValueError("domain_randomization['visual'] needs obs_type='so100_pixels_agent_pos'")
+            self._check_visual(domain_randomization["visual"])
         self.lib = _native.load()
         self.num_envs = int(num_envs)
         self.task = task
@@ -176,6 +182,7 @@ class SO100VecEnv:
             m0 = list(self.model.mocap_pos0) + list(self.model.mocap_quat0)
             self.mocap = torch.tensor(m0, dtype=f32, device=d).repeat(n, 1).contiguous()
         self.dr_params = None
+        self._visual = None
         self._flags = _native.SO100_FLAG_AUTORESET if self.autoreset else 0
         if domain_randomization:
             self.set_domain_randomization(**domain_randomization)
@@ -189,6 +196,8 @@ class SO100VecEnv:
             from .render import CameraRenderer
             self.renderer = CameraRenderer(self, observation_width, observation_height,
                                            channels_first=self.channels_first)
+            if self._visual is not None:
+                self._sample_views()
             self.pixels = self.renderer.pixels
             self.final_pixels = torch.zeros_like(self.pixels) if self.autoreset else None
             if flat_pixels:
@@ -229,12 +238,48 @@ class SO100VecEnv:
     def _stream(self):
         return _native.stream_ptr(_torch(), self.device)
 
-    def set_domain_randomization(self, mass=(0.8, 1.2), friction=(0.8, 1.2), action_noise=0.05, seed=None):
+    @staticmethod
+    def _check_visual(visual):
+        """The argument checks of a visual-randomisation dict (no device use); returns (ranges, per_episode, seed)."""
+        from .render import view_ranges
+        v = dict(visual)
+        per_episode, seed = bool(v.pop("per_episode", False)), v.pop("seed", None)
+        view_ranges(v, 0)
+        return v, per_episode, seed
+
+    def _sample_views(self, mask=None):
+        """Draw the view records (of the envs in mask): from the device episode counter with per_episode, else with
+        episode 0."""
+        ranges, per_episode, seed = self._visual
+        self.renderer.sample_views(ranges, seed, episode=self.episode if per_episode else None, mask=mask)
+
+    def set_domain_randomization(self, mass=(0.8, 1.2), friction=(0.8, 1.2), action_noise=0.05, seed=None, visual=None):
         """Per-env cube mass scale, contact friction scale (fixed per env) and action-noise sigma.
 
         The scales are a counter-based hash of (seed, global env id), so an env draws the same parameters
-        whatever the sharding (configs[4]: 32,768 envs over 4 GPUs)."""
+        whatever the sharding (configs[4]: 32,768 envs over 4 GPUs).
+
+        visual (pixel observations only; None = every env drawn from the one camera): a dict of the ranges each env's
+        view is drawn from, by the same hash (fields from 16 up) on the device: camera_pos (half-width, metres),
+        camera_rot_deg (half-width of a rotation vector's components about the camera's axes), fovy, ambient,
+        headlight, lights ((lo, hi) scales; lights: one pair or one per light), light_rot_deg (one rotation of every
+        light direction), colors (one (lo, hi) per-channel scale or a dict by render.MATERIALS name), per_episode
+        (default False: drawn once; True: an env's view is drawn again from its episode counter whenever it is reset,
+        the terminal image in final_pixels still showing the finished episode's view) and seed (default: the env's
+        base seed).  It touches images only; the physical part above applies as without it."""
         torch = _torch()
+        if visual is not None:
+            if self.obs_type != "so100_pixels_agent_pos":
+                raise ValueError("domain_randomization['visual'] needs obs_type='so100_pixels_agent_pos'")
+            ranges, per_episode, vseed = self._check_visual(visual)
+            self._visual = (ranges, per_episode, self.base_seed if vseed is None else int(vseed))
+        else:
+            self._visual = None
+        if getattr(self, "renderer", None) is not None:      # (the constructor samples once its renderer exists)
+            if self._visual is None:
+                self.renderer.views = None
+            else:
+                self._sample_views()
         s = self.base_seed if seed is None else int(seed)
         ids = np.arange(self.env_offset, self.env_offset + self.num_envs, dtype=np.uint64)
         p = torch.zeros(self.num_envs, 4, dtype=torch.float32)
@@ -273,6 +318,8 @@ class SO100VecEnv:
         _native.check(self.lib.so100_reset(self._handle, ctypes.byref(self._buf), mask_p, seeds_p, self._stream()),
                       "so100_reset")
         if self.renderer is not None:
+            if self._visual is not None and self._visual[1]:
+                self._sample_views(None if mask is None else self._mask)
             self._render_all()
         info = {"is_success": torch.zeros_like(self.success)}
         return self._observation(), info
@@ -339,6 +386,8 @@ class SO100VecEnv:
             self.renderer.render(out=self.final_pixels, mask=self._mask)
             _native.check(self.lib.so100_reset(self._handle, ctypes.byref(self._buf), _native.ptr(self._mask), None,
                                                s), "so100_reset")
+            if self._visual is not None and self._visual[1]:
+                self._sample_views(self._mask)         # the new episodes' views: final_pixels is already drawn
         self._render_all()
         return done
 

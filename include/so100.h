@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SO100_ABI_VERSION 19  /* 19: so100_render_to / so100_image_out (one render launch, several sinks: hwc, chw, flat float32);  18: env packing of the fused step (so100_set_env_packing, so100_env_packing, so100_env_order, so100_env_cost, so100_wave_cost);  17: so100_pool_stats (the fused step's contact-record pool, sized never to run out);  16: so100_source_hash;  15: the EE variant's mocap marker box collides (SO100_NGEOM 16, SO100_NPAIR 209, SO100_NCON_MAX 643, debug stride 3,922);  14: no per-env contact cap (SO100_NCON_MAX: every pair at its collider's maximum), debug stride 3,436 (SO100_DBG_OVF), ncon_dropped always 0, status -3 for a caught C++ exception;  13: so100_buffers.ep_return / ep_final / ep_accum (device-side episode statistics);  12: so100_model.convex (GJK/EPA mesh collider, MuJoCo 3.3.3 default), box-box up to 8 contacts, cube-table one convex contact;  11: so100_buffers.ncon_dropped, debug stride 160 (contact friction forces), so100_set_fused_build;  10: so100_hull_cells (MPR support lookup);  9: pad/link-hull pairs (SO100_NPAIR 191);  8: fused step kernel, so100_set_step_mode;  7: reward64 buffer;  6: Base hull + pad pairs (SO100_NPAIR 155, SO100_NHULL_ALL 10); 5: EE/mocap weld, render API */
+#define SO100_ABI_VERSION 20  /* 20: so100_view / so100_render_views / so100_render_materials / so100_views_sample / so100_view_bytes (camera, lights and colours per env);  19: so100_render_to / so100_image_out (one render launch, several sinks: hwc, chw, flat float32);  18: env packing of the fused step (so100_set_env_packing, so100_env_packing, so100_env_order, so100_env_cost, so100_wave_cost);  17: so100_pool_stats (the fused step's contact-record pool, sized never to run out);  16: so100_source_hash;  15: the EE variant's mocap marker box collides (SO100_NGEOM 16, SO100_NPAIR 209, SO100_NCON_MAX 643, debug stride 3,922);  14: no per-env contact cap (SO100_NCON_MAX: every pair at its collider's maximum), debug stride 3,436 (SO100_DBG_OVF), ncon_dropped always 0, status -3 for a caught C++ exception;  13: so100_buffers.ep_return / ep_final / ep_accum (device-side episode statistics);  12: so100_model.convex (GJK/EPA mesh collider, MuJoCo 3.3.3 default), box-box up to 8 contacts, cube-table one convex contact;  11: so100_buffers.ncon_dropped, debug stride 160 (contact friction forces), so100_set_fused_build;  10: so100_hull_cells (MPR support lookup);  9: pad/link-hull pairs (SO100_NPAIR 191);  8: fused step kernel, so100_set_step_mode;  7: reward64 buffer;  6: Base hull + pad pairs (SO100_NPAIR 155, SO100_NHULL_ALL 10); 5: EE/mocap weld, render API */
 
 /* tasks (gym_so100/__init__.py:4-32 ids; single_arm.py task classes) */
 #define SO100_TASK_CUBE_TO_BIN 0          /* gym_so100/SO100CubeToBin-v0, TimeLimit 700 */
@@ -246,6 +246,57 @@ typedef struct so100_image_out {
  * so100_render rejects.  so100_render is the hwc-only case of this call. */
 int so100_render_to(so100_env* env, const float* qpos, const uint8_t* mask, const so100_camera* cam, int width,
                     int height, const so100_image_out* out, void* stream);
+
+/* ---- (ABI 20) visual domain randomisation: camera, lights and colours per env.  The physical
+ * randomisation (SO100_FLAG_DR) leaves every image drawn from one camera under one set of lights; here env i is drawn
+ * from its own record views[i]. */
+#define SO100_NMATERIAL 5   /* 0 table, 1 bin, 2 arm light parts, 3 arm dark parts, 4 cube */
+typedef struct so100_view {          /* one per env, DEVICE memory, 40 dwords = 160 B */
+  float pos[3]; float mat[9]; float fovy;                    /* as so100_camera's */
+  float head_ambient, head_diffuse;
+  float light_diffuse[SO100_MAX_LIGHTS]; float light_dir[SO100_MAX_LIGHTS][3];
+  uint32_t rgb[SO100_NMATERIAL];     /* packed RGB8 base colour per material (R in bits 0-7, G 8-15, B 16-23) */
+  uint32_t reserved[4];
+} so100_view;
+int so100_view_bytes(void);          /* sizeof(so100_view) as compiled: lets bindings verify their mirror */
+/* Upload each triangle's material id (host [ntri], every id < SO100_NMATERIAL) for the mesh of the last
+ * so100_render_mesh call, which drops the ids of the mesh before it.  Nonzero for an ntri other than the mesh's or an id
+ * out of range. */
+int so100_render_materials(so100_env* env, const uint8_t* material, int ntri);
+/* so100_render_to with env i drawn from views[i] (device [N]): its pos, mat, fovy, headlight terms, light directions
+ * and diffuses, and as a triangle's base colour views[i].rgb[material].  cam supplies only the launch-uniform track,
+ * znear and nlight; with track = 1 the frame is the targetbody rule from the env's own pos (mat unused).  Nonzero
+ * (text in so100_last_error) for NULL views, no uploaded materials, and for what so100_render_to rejects. */
+int so100_render_views(so100_env* env, const float* qpos, const uint8_t* mask, const so100_camera* cam,
+                       const so100_view* views, int width, int height, const so100_image_out* out, void* stream);
+/* The ranges the records are drawn from.  Half-widths are symmetric about the base value, [lo, hi] pairs scale it;
+ * a range of zero width (half-width 0, lo = hi = 1) gives the base value bit for bit. */
+typedef struct so100_view_dr {
+  uint32_t size;                         /* sizeof(so100_view_dr): the callee rejects a mismatch */
+  uint32_t reserved0;
+  uint64_t seed;
+  float cam_pos;                         /* camera position half-width per axis, metres */
+  float cam_rot;                         /* half-width per component of a rotation vector about the camera's own axes,
+                                            radians: mat' = mat . Rodrigues(v) */
+  float fovy[2];                         /* scale of fovy */
+  float ambient[2], headlight[2];        /* scale of head_ambient, head_diffuse */
+  float light[SO100_MAX_LIGHTS][2];      /* scale of each directional light's diffuse (independent draws) */
+  float light_rot;                       /* half-width per component of one rotation vector (world axes) that turns
+                                            every light direction, radians */
+  float color[SO100_NMATERIAL][2];       /* per-channel scale of each material's base colour (three draws) */
+  float reserved1;
+} so100_view_dr;
+/* Fill views[i] (device [N]) of the envs whose mask byte is non-zero (device [N], NULL = all) on the device: every
+ * draw is a pure function of (dr->seed, global env id = env_offset + i, episode[i], field number), so the records
+ * depend neither on the sharding nor on the mask nor on launch order.  U[0,1) = the top 24 bits of
+ * splitmix64(splitmix64(seed ^ id * 0x100000001B3 ^ field * 0xD1B54A32D192ED03) + episode) / 2^24 (the hash of the
+ * physical randomisation's fields 1 and 2 with the episode mixed in); fields: 16-18 camera position x y z, 19-21
+ * camera rotation vector, 22 fovy, 23 ambient, 24 headlight, 25 + l light l, 29-31 light rotation vector,
+ * 32 + 3 material + channel colour.  Colour channel = floor(clip(base * s, 0, 1) * 255 + 0.5), base = base_rgb byte /
+ * 255.  cam: the base camera (host); base_rgb: host [SO100_NMATERIAL] packed RGB8; episode: device uint32 [N] or NULL
+ * = 0.  Enqueued on stream. */
+int so100_views_sample(so100_env* env, const so100_view_dr* dr, const so100_camera* cam, const uint32_t* base_rgb,
+                       const uint32_t* episode, const uint8_t* mask, so100_view* views, void* stream);
 
 /* Batched sparse GoalEnv reward (env.py:341-353): out[i] = ||a_i - d_i|| < threshold ? 0 : -1. */
 int so100_goal_reward(so100_env* env, int n, const float* achieved, const float* desired, float* out,
