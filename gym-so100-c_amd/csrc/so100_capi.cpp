@@ -32,6 +32,9 @@ hipError_t launch_render(const DevModel*, const float4*, const int*, const uint3
 hipError_t launch_render_views(const DevModel*, const float4*, const int*, const uint8_t*, int, const float*,
                                const uint8_t*, const so100_camera&, const so100_view*, int, int, int,
                                const so100_image_out&, hipStream_t);
+hipError_t launch_render_aux(const DevModel*, const float4*, const int*, const uint32_t*, const uint8_t*, const uint8_t*,
+                             int, const float*, const uint8_t*, const so100_camera&, const so100_view*, int, int, int,
+                             const so100_image_out&, const so100_aux_out&, hipStream_t);
 hipError_t launch_views_sample(const so100_view_dr&, const so100_camera&, const uint32_t*, const uint32_t*,
                                const uint8_t*, so100_view*, int, int, hipStream_t);
 hipError_t alloc_workspace(int, Workspace*);
@@ -90,6 +93,7 @@ struct so100_env {
   uint32_t* r_rgb = nullptr;
   int r_ntri = 0;
   uint8_t* r_mat = nullptr;     // per-triangle material ids of that mesh (so100_render_materials), or none yet
+  uint8_t* r_label = nullptr;   // per-triangle labels of that mesh (so100_render_labels), or none yet
   // profiling (so100_profile_enable): events[step][prof_per] (2 nsubstep + 2 split, 2 fused)
   std::vector<hipEvent_t> prof_ev;
   int prof_cap = 0, prof_used = 0, prof_per = 0;
@@ -790,6 +794,7 @@ static int so100_destroy_impl(so100_env* env) {
   if (env->r_body) (void)hipFree(env->r_body);
   if (env->r_rgb) (void)hipFree(env->r_rgb);
   if (env->r_mat) (void)hipFree(env->r_mat);
+  if (env->r_label) (void)hipFree(env->r_label);
   hipError_t e = hipFree(env->d_model);
   if (env->d_cand) (void)hipFree(env->d_cand);
   hipError_t e2 = free_chunks(env);
@@ -1184,7 +1189,9 @@ static int so100_render_mesh_impl(so100_env* env, const float* tri, const int* b
   if (env->r_body) (void)hipFree(env->r_body);
   if (env->r_rgb) (void)hipFree(env->r_rgb);
   if (env->r_mat) (void)hipFree(env->r_mat);
-  env->r_tri = nullptr; env->r_body = nullptr; env->r_rgb = nullptr; env->r_mat = nullptr; env->r_ntri = 0;
+  if (env->r_label) (void)hipFree(env->r_label);
+  env->r_tri = nullptr; env->r_body = nullptr; env->r_rgb = nullptr; env->r_mat = nullptr; env->r_label = nullptr;
+  env->r_ntri = 0;
   hipError_t e = hipMalloc(&env->r_tri, t.size() * sizeof(float4));
   if (e == hipSuccess) e = hipMalloc(&env->r_body, (size_t)ntri * sizeof(int));
   if (e == hipSuccess) e = hipMalloc(&env->r_rgb, (size_t)ntri * sizeof(uint32_t));
@@ -1196,18 +1203,20 @@ static int so100_render_mesh_impl(so100_env* env, const float* tri, const int* b
   return 0;
 }
 
-// the one render launch behind so100_render (hwc alone), so100_render_to and, with a record per env (views != nullptr),
-// so100_render_views; `who` names the entry point in errors
+// the one render launch behind so100_render (hwc alone), so100_render_to, with a record per env (views != nullptr)
+// so100_render_views and, with the depth / label sinks (aux != nullptr, views or not), so100_render_aux; `who` names the
+// entry point in errors
 static int render_launch(const char* who, so100_env* env, const float* qpos, const uint8_t* mask, const so100_camera* cam,
                          int width, int height, const so100_image_out& o, void* stream,
-                         const so100_view* views = nullptr) {
+                         const so100_view* views = nullptr, const so100_aux_out* aux = nullptr) {
   char msg[160];
   auto bad = [&](const char* what) {
     snprintf(msg, sizeof(msg), "%s: %s", who, what);
     return fail(msg);
   };
   if (!env || !qpos || !cam) return bad("bad arguments");
-  if (!o.hwc && !o.chw && !o.flat) return bad("no sink (hwc, chw and flat are all NULL)");
+  // (so100_render_aux has looked for a sink across both structs before it comes here)
+  if (!aux && !o.hwc && !o.chw && !o.flat) return bad("no sink (hwc, chw and flat are all NULL)");
   if (env->r_ntri <= 0) return bad("no render mesh (so100_render_mesh)");
   if (width <= 0 || height <= 0 || width > 4096 || (long)width * height > (1L << 22))
     return bad("bad image size (width <= 4096, width*height <= 2^22)");
@@ -1215,7 +1224,14 @@ static int render_launch(const char* who, so100_env* env, const float* qpos, con
   if (cam->nlight < 0 || cam->nlight > SO100_MAX_LIGHTS || !(cam->fovy > 0.f && cam->fovy < 180.f))
     return bad("bad camera");
   if (views && !env->r_mat) return bad("no materials (so100_render_materials)");
+  if (aux && aux->label && !env->r_label) return bad("no labels (so100_render_labels)");
   DeviceGuard g(env->device);
+  if (aux) {
+    hipError_t e = so100::launch_render_aux(env->d_model, env->r_tri, env->r_body, env->r_rgb, env->r_mat, env->r_label,
+                                            env->r_ntri, qpos, mask, *cam, views, env->n, width, height, o, *aux,
+                                            (hipStream_t)stream);
+    return e == hipSuccess ? 0 : fail_hip(who, e);
+  }
   hipError_t e = views ? so100::launch_render_views(env->d_model, env->r_tri, env->r_body, env->r_mat, env->r_ntri, qpos,
                                                     mask, *cam, views, env->n, width, height, o, (hipStream_t)stream)
                        : so100::launch_render(env->d_model, env->r_tri, env->r_body, env->r_rgb, env->r_ntri, qpos, mask,
@@ -1284,6 +1300,45 @@ static int so100_render_views_impl(so100_env* env, const float* qpos, const uint
   return render_launch("so100_render_views", env, qpos, mask, cam, width, height, *out, stream, views);
 }
 
+static int so100_render_labels_impl(so100_env* env, const uint8_t* label, int ntri) {
+  if (!env || !label) return fail("so100_render_labels: bad arguments");
+  if (env->r_ntri <= 0) return fail("so100_render_labels: no render mesh (so100_render_mesh)");
+  if (ntri != env->r_ntri) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "so100_render_labels: ntri %d, the mesh has %d", ntri, env->r_ntri);
+    return fail(msg);
+  }
+  for (int i = 0; i < ntri; i++)
+    if (label[i] == 255) return fail("so100_render_labels: label 255 is the background's");
+  DeviceGuard g(env->device);
+  hipError_t e = hipSuccess;
+  if (!env->r_label) e = hipMalloc(&env->r_label, (size_t)ntri);
+  if (e == hipSuccess) e = hipMemcpy(env->r_label, label, (size_t)ntri, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (env->r_label) (void)hipFree(env->r_label);
+    env->r_label = nullptr;
+    return fail_hip("so100_render_labels", e);
+  }
+  return 0;
+}
+
+static int so100_render_aux_impl(so100_env* env, const float* qpos, const uint8_t* mask, const so100_camera* cam,
+                                 const so100_view* views, int width, int height, const so100_image_out* out,
+                                 const so100_aux_out* aux, void* stream) {
+  // the structs' sizes first: nothing else of them is read before they are known to be this library's layout
+  if (out && out->size != sizeof(so100_image_out))
+    return size_mismatch("so100_render_aux", "so100_image_out", out->size, sizeof(so100_image_out));
+  if (aux && aux->size != sizeof(so100_aux_out))
+    return size_mismatch("so100_render_aux", "so100_aux_out", aux->size, sizeof(so100_aux_out));
+  if (!(out && (out->hwc || out->chw || out->flat)) && !(aux && (aux->depth || aux->label)))
+    return fail("so100_render_aux: no sink (hwc, chw, flat, depth and label are all NULL)");
+  if (!env) return fail("so100_render_aux: NULL env");
+  const so100_image_out none{(uint32_t)sizeof(so100_image_out), nullptr, nullptr, nullptr, 0};
+  const so100_aux_out no_aux{(uint32_t)sizeof(so100_aux_out), nullptr, nullptr};
+  return render_launch("so100_render_aux", env, qpos, mask, cam, width, height, out ? *out : none, stream, views,
+                       aux ? aux : &no_aux);
+}
+
 static int so100_views_sample_impl(so100_env* env, const so100_view_dr* dr, const so100_camera* cam,
                                    const uint32_t* base_rgb, const uint32_t* episode, const uint8_t* mask,
                                    so100_view* views, void* stream) {
@@ -1323,6 +1378,26 @@ int so100_render_views(so100_env* env, const float* qpos, const uint8_t* mask, c
     return so100_render_views_impl(env, qpos, mask, cam, views, width, height, out, stream);
   } catch (...) {
     return caught("so100_render_views");
+  }
+}
+
+int so100_aux_out_bytes(void) { return (int)sizeof(so100_aux_out); }
+
+int so100_render_labels(so100_env* env, const uint8_t* label, int ntri) {
+  try {
+    return so100_render_labels_impl(env, label, ntri);
+  } catch (...) {
+    return caught("so100_render_labels");
+  }
+}
+
+int so100_render_aux(so100_env* env, const float* qpos, const uint8_t* mask, const so100_camera* cam,
+                     const so100_view* views, int width, int height, const so100_image_out* out,
+                     const so100_aux_out* aux, void* stream) {
+  try {
+    return so100_render_aux_impl(env, qpos, mask, cam, views, width, height, out, aux, stream);
+  } catch (...) {
+    return caught("so100_render_aux");
   }
 }
 

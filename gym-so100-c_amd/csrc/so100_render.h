@@ -1,7 +1,8 @@
-// so100_render.h - the render kernel's body, shared by its three launches: so100_render.hip (the hwc image alone),
-// so100_render_sinks.hip (so100_render_to's further sinks) and so100_render_views.hip (so100_render_views: camera,
-// lights and colours per env).  One translation unit per kernel: with two instantiations in one unit the hwc-only
-// kernel was scheduled differently and measured slower.
+// so100_render.h - the render kernel's body, shared by its four launches: so100_render.hip (the hwc image alone),
+// so100_render_sinks.hip (so100_render_to's further sinks), so100_render_views.hip (so100_render_views: camera,
+// lights and colours per env) and so100_render_aux.hip (so100_render_aux: the depth and label sinks, with or without
+// views).  One translation unit per kernel: with two instantiations in one unit the hwc-only kernel was scheduled
+// differently and measured slower.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -42,6 +43,15 @@ struct RenderSinkArgs : RenderArgs {
 struct RenderViewArgs : RenderSinkArgs {
   const so100_view* views;              // [n]
   const uint8_t* material;              // [ntri] material id < SO100_NMATERIAL: the base colour is views[env].rgb[id]
+};
+// the launch with the depth and label sinks (so100_render_aux).  Its key carries a label under the colour:
+// depth bits << 32 | RGB8 << 8 | label, so colour still orders equal depths as in the other three kernels and the label
+// orders what is left.  views may be null (uniform per launch): the LDS record is then filled from a.cam and the base
+// colour is tri_rgb[t]
+struct RenderAuxArgs : RenderViewArgs {
+  const uint8_t* label;                 // [ntri] label < 255, or null (every triangle 0; no seg sink then)
+  float* depth;                         // [n][height][width] or null: 1 / izp of the winning key; background 0.0f
+  uint8_t* seg;                         // [n][height][width] or null: the winning key's label; background 255
 };
 constexpr int kViewWords = (int)(sizeof(so100_view) / sizeof(uint32_t));
 static_assert(sizeof(so100_view) == 160 && kViewWords == 40, "so100_view: 40 dwords");
@@ -92,17 +102,20 @@ DEV uint32_t shade(const Cam& c, int nlight, const float* cm, const float* p0, c
 // the camera-like record the body reads: a.cam, or with views the env's record in LDS
 template <class Args>
 DEV decltype(auto) view_source(const Args& a, const ViewLds& vl) {
-  if constexpr (std::is_same<Args, RenderViewArgs>::value) return (vl.v);
+  if constexpr (std::is_same<Args, RenderViewArgs>::value || std::is_same<Args, RenderAuxArgs>::value) return (vl.v);
   else return (a.cam);
 }
 
 // Args = RenderArgs: the hwc image alone (so100_render and every hwc-only so100_render_to);
 // Args = RenderSinkArgs: every non-null sink of a.out / a.chw / a.flat is written from the same band;
-// Args = RenderViewArgs: the same sinks, drawn from views[env] (not referenced, vl costs the other two no LDS).
+// Args = RenderViewArgs: the same sinks, drawn from views[env] (not referenced, vl costs the other two no LDS);
+// Args = RenderAuxArgs: those sinks and a.depth / a.seg, from views[env] or (a.views null) from a.cam through vl.
 template <class Args>
 __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
   constexpr bool kSinks = sizeof(Args) != sizeof(RenderArgs);
   constexpr bool kView = std::is_same<Args, RenderViewArgs>::value;
+  constexpr bool kAux = std::is_same<Args, RenderAuxArgs>::value;
+  constexpr int kColShift = kAux ? 8 : 0;                  // the colour's place in the key's lower half
   __shared__ ViewLds vl;
   __shared__ EnvShared sh;
   __shared__ float frm[SO100_NBODY][12];           // body rotation (9) + position (3)
@@ -119,6 +132,23 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
   if (tid < SO100_NQ) sh.qpos[tid] = a.qpos[(size_t)env * SO100_NQ + tid];
   if constexpr (kView) {
     if (tid < kViewWords) vl.w[tid] = reinterpret_cast<const uint32_t*>(a.views + env)[tid];
+  }
+  if constexpr (kAux) {
+    if (a.views) {                                         // uniform per launch
+      if (tid < kViewWords) vl.w[tid] = reinterpret_cast<const uint32_t*>(a.views + env)[tid];
+    } else if (tid == 0) {
+      // the base camera as a record (what an identity record holds, bit for bit); rgb is not read without views
+      so100_view& v = vl.v;
+      for (int k = 0; k < 3; k++) v.pos[k] = a.cam.pos[k];
+      for (int k = 0; k < 9; k++) v.mat[k] = a.cam.mat[k];
+      v.fovy = a.cam.fovy;
+      v.head_ambient = a.cam.head_ambient;
+      v.head_diffuse = a.cam.head_diffuse;
+      for (int l = 0; l < SO100_MAX_LIGHTS; l++) {
+        v.light_diffuse[l] = a.cam.light_diffuse[l];
+        for (int k = 0; k < 3; k++) v.light_dir[l][k] = a.cam.light_dir[l][k];
+      }
+    }
   }
   const auto& cv = view_source(a, vl);                     // read after the barrier below
   __syncthreads();
@@ -211,8 +241,10 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
       if (bx0 > bx1 || by0 > by1) return false;
       uint32_t base;
       if constexpr (kView) base = cv.rgb[a.material[t]];
+      else if constexpr (kAux) base = a.views ? cv.rgb[a.material[t]] : a.tri_rgb[t];
       else base = a.tri_rgb[t];
       col = shade(cv, a.cam.nlight, cmat, pw[0], pw[1], pw[2], base);
+      if constexpr (kAux) col = (col << 8) | (a.label ? (uint32_t)a.label[t] : 0u);   // the key's lower half
       return true;
     };
     // one pixel of a set-up triangle: edge functions at the pixel centre, perspective-correct depth
@@ -271,7 +303,7 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
       // channel c of band pixel i (background: 0)
       auto chan = [&](int i, int c) -> uint32_t {
         const unsigned long long key = zb[i];
-        return key == ~0ull ? 0u : ((uint32_t)key >> (8 * c)) & 0xFFu;
+        return key == ~0ull ? 0u : ((uint32_t)key >> (8 * c + kColShift)) & 0xFFu;
       };
       if (a.out) {                                            // uniform per launch
         for (int i = tid; i < npx; i += kRenderThreads) {
@@ -307,6 +339,32 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
         for (int j = tid; j < 3 * npx; j += kRenderThreads) {
           const int i = j / 3;
           f[j] = kByteUnit.v[chan(i, j - 3 * i)];
+        }
+      }
+      if constexpr (kAux) {
+        if (a.depth) {
+          // the float32 the depth test compared: the key's upper half as it is (the empty key gives 0.0f)
+          float* d = a.depth + ((size_t)env * H + y0) * W;
+          for (int i = tid; i < npx; i += kRenderThreads) {
+            const unsigned long long key = zb[i];
+            d[i] = key == ~0ull ? 0.f : __uint_as_float((uint32_t)(key >> 32));
+          }
+        }
+        if (a.seg) {
+          // the key's low byte (the empty key's is 255, the background label); the chw plane's head / dword / tail
+          // scheme on the band's span [p, p + npx): nothing outside it is touched
+          uint8_t* p = a.seg + ((size_t)env * H + y0) * W;
+          const int head = min(npx, (int)((4u - (uint32_t)((uintptr_t)p & 3u)) & 3u));
+          const int nquad = (npx - head) >> 2;
+          const int tail = head + 4 * nquad;
+          uint32_t* q = (uint32_t*)(p + head);                // 4-byte aligned (unused when nquad == 0)
+          auto lab = [&](int i) -> uint32_t { return (uint32_t)zb[i] & 0xFFu; };
+          for (int k = tid; k < nquad; k += kRenderThreads) {
+            const int i = head + 4 * k;
+            q[k] = lab(i) | (lab(i + 1) << 8) | (lab(i + 2) << 16) | (lab(i + 3) << 24);
+          }
+          if (tid < head) p[tid] = (uint8_t)lab(tid);         // head < 4
+          if (tid < npx - tail) p[tail + tid] = (uint8_t)lab(tail + tid);   // npx - tail < 4
         }
       }
     }

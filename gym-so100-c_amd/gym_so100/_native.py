@@ -48,6 +48,15 @@ class SO100ImageOut(ctypes.Structure):
         super().__init__(ctypes.sizeof(SO100ImageOut), hwc, chw, flat, flat_pitch)
 
 
+class SO100AuxOut(ctypes.Structure):
+    """Mirror of ``so100_aux_out`` (include/so100.h): the depth and label sinks of one ``so100_render_aux`` launch,
+    NULL = not written.  ``size`` is set to the mirror's size, which the callee checks against its own."""
+    _fields_ = [("size", ctypes.c_uint32), ("depth", _P), ("label", _P)]
+
+    def __init__(self, depth=None, label=None):
+        super().__init__(ctypes.sizeof(SO100AuxOut), depth, label)
+
+
 SO100_NMATERIAL = 5
 
 
@@ -89,7 +98,7 @@ class NativeLibraryError(RuntimeError):
 _lib = None
 
 
-ABI_VERSION = 20         # include/so100.h SO100_ABI_VERSION
+ABI_VERSION = 21         # include/so100.h SO100_ABI_VERSION
 HULL_CELLG = 8           # SO100_HULL_CELLG
 HULL_NCELL = 6 * HULL_CELLG * HULL_CELLG
 
@@ -135,6 +144,10 @@ def load():
     lib.so100_render_views.argtypes = [_P, _P, _P, ctypes.POINTER(SO100Camera), _P, ctypes.c_int, ctypes.c_int,
                                        ctypes.POINTER(SO100ImageOut), _P]
     lib.so100_views_sample.argtypes = [_P, ctypes.POINTER(SO100ViewDR), ctypes.POINTER(SO100Camera), _P, _P, _P, _P, _P]
+    lib.so100_aux_out_bytes.argtypes = []
+    lib.so100_render_labels.argtypes = [_P, _P, ctypes.c_int]
+    lib.so100_render_aux.argtypes = [_P, _P, _P, ctypes.POINTER(SO100Camera), _P, ctypes.c_int, ctypes.c_int,
+                                     ctypes.POINTER(SO100ImageOut), ctypes.POINTER(SO100AuxOut), _P]
     lib.so100_hull_cells.argtypes = [_P, _P, _P, ctypes.c_int]
     lib.so100_set_fused_build.argtypes = [_P, ctypes.c_int]
     lib.so100_fused_build.argtypes = [_P, ctypes.c_int]
@@ -149,7 +162,8 @@ def load():
                "so100_pool_stats", "so100_chunk_info", "so100_render_mesh", "so100_render", "so100_render_to", "so100_set_step_mode", "so100_step_mode", "so100_hull_cells",
                "so100_set_fused_build", "so100_fused_build", "so100_set_env_packing", "so100_env_packing",
                "so100_env_order", "so100_env_cost", "so100_wave_cost", "so100_view_bytes", "so100_render_materials",
-               "so100_render_views", "so100_views_sample"):
+               "so100_render_views", "so100_views_sample", "so100_aux_out_bytes", "so100_render_labels",
+               "so100_render_aux"):
         getattr(lib, fn).restype = ctypes.c_int
     lib.so100_struct_sizes.argtypes = [_P, _P]
     lib.so100_struct_sizes.restype = ctypes.c_int
@@ -164,6 +178,9 @@ def load():
     if lib.so100_view_bytes() != ctypes.sizeof(SO100View):
         raise NativeLibraryError(f"struct layout mismatch: so100_view {lib.so100_view_bytes()} vs "
                                  f"{ctypes.sizeof(SO100View)}")
+    if lib.so100_aux_out_bytes() != ctypes.sizeof(SO100AuxOut):
+        raise NativeLibraryError(f"struct layout mismatch: so100_aux_out {lib.so100_aux_out_bytes()} vs "
+                                 f"{ctypes.sizeof(SO100AuxOut)}")
     _lib = lib
     return lib
 
@@ -176,7 +193,8 @@ EXPORTED_SYMBOLS = ("so100_abi_version", "so100_last_error", "so100_source_hash"
                     "so100_set_step_mode", "so100_step_mode", "so100_hull_cells", "so100_set_fused_build",
                     "so100_fused_build", "so100_set_env_packing", "so100_env_packing", "so100_env_order",
                     "so100_env_cost", "so100_wave_cost", "so100_view_bytes", "so100_render_materials",
-                    "so100_render_views", "so100_views_sample")
+                    "so100_render_views", "so100_views_sample", "so100_aux_out_bytes", "so100_render_labels",
+                    "so100_render_aux")
 
 
 def source_hash():

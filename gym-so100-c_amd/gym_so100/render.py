@@ -13,6 +13,11 @@ Visual domain randomisation: with ``CameraRenderer.views`` set (a device [N, 40]
 ``identity_views`` / ``sample_views``) env i is drawn from its own camera pose, field of view, lights and material
 colours (C-ABI ``so100_render_views``); without it every env is drawn from the one camera, as before.
 
+Depth and segmentation: ``CameraRenderer(depth=True, segmentation=True)`` also keeps ``depth`` (float32 [N, H, W]: metres
+along the camera's viewing axis, background 0) and ``segmentation`` (uint8 [N, H, W]: the class of ``segment_labels``,
+background ``SEG_BACKGROUND``), what dm_control's ``physics.render(depth=True / segmentation=True)`` returns, written by
+the launch that draws the colour image (C-ABI ``so100_render_aux``).
+
 It is a rasteriser of its own, not MuJoCo's OpenGL pipeline: geometry and colours are the scene's, the
 pixel values are not MuJoCo's (no specular, shadows, fog or anti-aliasing).
 """
@@ -28,6 +33,9 @@ CAMERAS = ("top", "angle", "left_pillar", "right_pillar", "front_close")
 TRACKING = ("front_close",)              # mode="targetbody" on the ee body: frame per env
 ZNEAR = 0.01
 MATERIALS = ("table", "bin", "arm_light", "arm_dark", "cube")      # SO100_NMATERIAL ids 0..4 (include/so100.h)
+# segmentation classes (segment_labels): label k is SEG_CLASSES[k], a pixel no triangle covers is SEG_BACKGROUND
+SEG_CLASSES = ("table", "bin", "Base", "link1", "link2", "link3", "link4", "link5", "link6", "cube")
+SEG_BACKGROUND = 255
 # the keys of a visual-randomisation dict (SO100VecEnv.set_domain_randomization(visual=...), sample_views(ranges))
 VISUAL_KEYS = ("camera_pos", "camera_rot_deg", "fovy", "ambient", "headlight", "lights", "light_rot_deg", "colors",
                "per_episode", "seed")
@@ -93,6 +101,25 @@ def material_ids(scene):
     return ids, base
 
 
+def segment_labels(scene):
+    """(labels uint8 [ntri], names): each triangle's segmentation class: 0 table and 1 bin (the world body's triangles,
+    told apart by material_ids), 2 the Base (body 1), 3-8 the six arm links (bodies 2-7), 9 the cube (body 8); names[k]
+    is class k's.  ValueError for a triangle that fits no class."""
+    body = np.asarray(scene["body"])
+    world = body == 0
+    mat, _ = material_ids({"body": body[world], "rgb": np.asarray(scene["rgb"])[world]})     # the world body's alone
+    lab = np.full(len(body), SEG_BACKGROUND, dtype=np.uint8)
+    lab[np.nonzero(world)[0][mat == MATERIALS.index("table")]] = 0
+    lab[np.nonzero(world)[0][mat == MATERIALS.index("bin")]] = 1
+    for b in range(1, 9):
+        lab[body == b] = b + 1
+    bad = np.nonzero(lab == SEG_BACKGROUND)[0]
+    if len(bad):
+        raise ValueError(f"{len(bad)} triangles fit no segmentation class of {SEG_CLASSES}, the first: triangle "
+                         f"{int(bad[0])} (body {int(body[bad[0]])})")
+    return lab, SEG_CLASSES
+
+
 def pack_rgb8(rgb):
     """float32 [..., 3] in [0, 1] -> packed RGB8 as so100_render_mesh packs tri_rgb (float32 x * 255 + 0.5, truncated)"""
     x = np.clip(np.asarray(rgb, dtype=np.float32), np.float32(0), np.float32(1))
@@ -150,9 +177,14 @@ class CameraRenderer:
 
     channels_first: ``pixels`` (and every ``out``) is [N,3,H,W], the layout SB3's image policies take, written by
     the render kernel itself (C-ABI ``so100_render_to``, chw sink) instead of a transpose afterwards; the default
-    [N,H,W,3] is the reference's."""
+    [N,H,W,3] is the reference's.
 
-    def __init__(self, venv, width=640, height=480, camera="top", channels_first=False):
+    depth / segmentation: also keep ``depth`` (float32 [N,H,W], metres along the viewing axis, background 0) and / or
+    ``segmentation`` (uint8 [N,H,W], segment_labels' classes, background SEG_BACKGROUND), filled by the launch that
+    draws ``pixels`` (C-ABI ``so100_render_aux``).  They have no channel axis: channels_first does not touch them."""
+
+    def __init__(self, venv, width=640, height=480, camera="top", channels_first=False, depth=False,
+                 segmentation=False):
         torch = _torch()
         self.venv = venv
         self.width, self.height = int(width), int(height)
@@ -169,6 +201,9 @@ class CameraRenderer:
         _native.check(venv.lib.so100_render_materials(venv._handle, mat.ctypes.data, len(mat)),
                       "so100_render_materials")
         self.base_rgb = np.ascontiguousarray(pack_rgb8(base), dtype=np.uint32)       # [5] packed RGB8 per material
+        # so do the labels, read only by render_aux's label sink
+        lab, _ = segment_labels(scene)
+        _native.check(venv.lib.so100_render_labels(venv._handle, lab.ctypes.data, len(lab)), "so100_render_labels")
         self.views = None                # [N, 40] int32 device tensor of so100_view records, or None: one camera
         self.camera_name = camera
         self.camera = make_camera(scene, camera)
@@ -176,6 +211,10 @@ class CameraRenderer:
         self.channels_first = bool(channels_first)
         self.image_shape = (3, self.height, self.width) if self.channels_first else (self.height, self.width, 3)
         self.pixels = torch.zeros(venv.num_envs, *self.image_shape, dtype=torch.uint8, device=venv.device)
+        self.depth = torch.zeros(venv.num_envs, self.height, self.width, dtype=torch.float32,
+                                 device=venv.device) if depth else None
+        self.segmentation = torch.full((venv.num_envs, self.height, self.width), SEG_BACKGROUND, dtype=torch.uint8,
+                                       device=venv.device) if segmentation else None
 
     def identity_views(self):
         """Set ``views`` to the base view in every env (the renderer's camera, the scene's lights and colours): the
@@ -206,7 +245,7 @@ class CameraRenderer:
                                                _native.ptr(self.views), v._stream()), "so100_views_sample")
         return self.views
 
-    def render(self, qpos=None, out=None, mask=None, flat=None, views=None):
+    def render(self, qpos=None, out=None, mask=None, flat=None, views=None, depth=None, segmentation=None):
         """Enqueue the render of qpos (default: the env's state) into out (default self.pixels); mask: [N]
         bool/uint8 device tensor of the envs to draw (the others keep their previous image and flat row).
 
@@ -216,7 +255,11 @@ class CameraRenderer:
 
         views: an [N, 40] int32 device tensor of so100_view records (default ``self.views``); when there is one, env i
         is drawn from record i (C-ABI so100_render_views), otherwise the calls are those of a renderer without
-        views."""
+        views.
+
+        depth, segmentation: contiguous [N, H, W] device tensors, float32 and uint8 (defaults ``self.depth`` and
+        ``self.segmentation``); when there is either, the launch is so100_render_aux and fills them with the image,
+        otherwise every call is the one of a renderer without them."""
         torch = _torch()
         v = self.venv
         q = v.qpos if qpos is None else qpos
@@ -236,7 +279,14 @@ class CameraRenderer:
         if vw is not None and (vw.shape != (v.num_envs, _native.VIEW_WORDS) or vw.element_size() != 4 or
                                not vw.is_contiguous() or vw.device != o.device):
             raise ValueError("views must be a contiguous 4-byte [N, 40] device tensor")
-        if flat is None and not self.channels_first and vw is None:
+        dp = self.depth if depth is None else depth
+        sg = self.segmentation if segmentation is None else segmentation
+        for t, dt, what in ((dp, torch.float32, "depth must be a contiguous float32"),
+                            (sg, torch.uint8, "segmentation must be a contiguous uint8")):
+            if t is not None and (t.shape != (v.num_envs, self.height, self.width) or t.dtype != dt or
+                                  not t.is_contiguous() or t.device != o.device):
+                raise ValueError(what + " [N, H, W] device tensor")
+        if flat is None and not self.channels_first and vw is None and dp is None and sg is None:
             _native.check(v.lib.so100_render(v._handle, _native.ptr(q), _native.ptr(m), ctypes.byref(self.camera),
                                              self.width, self.height, _native.ptr(o), v._stream()), "so100_render")
             return o
@@ -249,6 +299,12 @@ class CameraRenderer:
         sinks = _native.SO100ImageOut(hwc=None if self.channels_first else _native.ptr(o),
                                       chw=_native.ptr(o) if self.channels_first else None,
                                       flat=_native.ptr(flat), flat_pitch=pitch)
+        if dp is not None or sg is not None:
+            aux = _native.SO100AuxOut(depth=_native.ptr(dp), label=_native.ptr(sg))
+            _native.check(v.lib.so100_render_aux(v._handle, _native.ptr(q), _native.ptr(m), ctypes.byref(self.camera),
+                                                 _native.ptr(vw), self.width, self.height, ctypes.byref(sinks),
+                                                 ctypes.byref(aux), v._stream()), "so100_render_aux")
+            return o
         if vw is not None:
             _native.check(v.lib.so100_render_views(v._handle, _native.ptr(q), _native.ptr(m), ctypes.byref(self.camera),
                                                    _native.ptr(vw), self.width, self.height, ctypes.byref(sinks),

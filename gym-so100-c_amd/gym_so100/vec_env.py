@@ -109,13 +109,20 @@ class SO100VecEnv:
             in the launch that fills ``pixels``, and reset / step copy agent_pos into its last six columns.  The
             GoalEnv then returns it as ``"observation"`` (the same tensor every call, overwritten by the next step);
             without the flag that observation is built by torch on every call.
+        depth, segmentation: pixel observations only: the observation dict gains ``"depth"`` (float32 [N,H,W], metres
+            along the camera's viewing axis, background 0) and / or ``"segmentation"`` (uint8 [N,H,W], the classes of
+            render.segment_labels, background render.SEG_BACKGROUND), what dm_control's physics.render(depth=True /
+            segmentation=True) returns, drawn by the launch that draws ``pixels``.  With auto-reset ``final_depth`` /
+            ``final_segmentation`` ride in ``info["final_observation"]`` beside ``final_pixels``.  The GoalEnv's
+            flattened ``"observation"`` stays as it is; the two tensors are further keys of its dict.  ValueError with
+            any other obs_type.
     """
 
     def __init__(self, num_envs, task="so100_cube_to_bin", obs_type="so100_state", device="cuda:0", seed=0,
                  max_episode_steps=None, autoreset=True, domain_randomization=None, env_offset=0,
                  iterations=None, debug=False, solver="newton", observation_width=640, observation_height=480,
                  variant="joint", reward64=False, nsubstep=None, convex="epa", episode_stats=False, channels_first=False,
-                 flat_pixels=False):
+                 flat_pixels=False, depth=False, segmentation=False):
         torch = _torch()
         if obs_type not in ("so100_state", "so100_pixels_agent_pos"):
             raise NotImplementedError(f"obs_type={obs_type!r}: 'so100_state' or 'so100_pixels_agent_pos'")
@@ -125,6 +132,8 @@ class SO100VecEnv:
             raise ValueError("channels_first: the GoalEnv's flattened pixel observation is HWC (env.py:267-270)")
         if (channels_first or flat_pixels) and obs_type != "so100_pixels_agent_pos":
             raise ValueError("channels_first / flat_pixels need obs_type='so100_pixels_agent_pos'")
+        if (depth or segmentation) and obs_type != "so100_pixels_agent_pos":
+            raise ValueError("depth / segmentation need obs_type='so100_pixels_agent_pos'")
         if domain_randomization and domain_randomization.get("visual") is not None:
             if obs_type != "so100_pixels_agent_pos":
                 raise ValueError("domain_randomization['visual'] needs obs_type='so100_pixels_agent_pos'")
@@ -191,15 +200,22 @@ class SO100VecEnv:
         self._seeds = torch.zeros(n, dtype=i32, device=d)
         self._mask = torch.zeros(n, dtype=torch.uint8, device=d)
         self.pixels = self.final_pixels = self.renderer = self.pixels_flat = None
+        self.depth = self.segmentation = self.final_depth = self.final_segmentation = None
         self.channels_first = bool(channels_first)
         if obs_type == "so100_pixels_agent_pos":
-            from .render import CameraRenderer
+            from .render import CameraRenderer, SEG_BACKGROUND
             self.renderer = CameraRenderer(self, observation_width, observation_height,
-                                           channels_first=self.channels_first)
+                                           channels_first=self.channels_first, depth=depth,
+                                           segmentation=segmentation)
             if self._visual is not None:
                 self._sample_views()
             self.pixels = self.renderer.pixels
             self.final_pixels = torch.zeros_like(self.pixels) if self.autoreset else None
+            self.depth, self.segmentation = self.renderer.depth, self.renderer.segmentation
+            if self.autoreset:
+                self.final_depth = None if self.depth is None else torch.zeros_like(self.depth)
+                self.final_segmentation = None if self.segmentation is None else \
+                    torch.full_like(self.segmentation, SEG_BACKGROUND)
             if flat_pixels:
                 self._npix = 3 * self.renderer.width * self.renderer.height
                 self.pixels_flat = torch.zeros(n, self._npix + 6, dtype=f32, device=d)
@@ -352,8 +368,9 @@ class SO100VecEnv:
         info = {"is_success": self.success, "diverged": self.diverged, "contact_bits": self.contact_bits,
                 "ncon_dropped": self.ncon_dropped}
         if self.autoreset:
-            info["final_observation"] = self.final_obs if self.renderer is None else \
-                {"pixels": self.final_pixels, "agent_pos": self.final_obs[:, 9:15]}
+            info["final_observation"] = self.final_obs if self.renderer is None else self._with_aux(
+                {"pixels": self.final_pixels, "agent_pos": self.final_obs[:, 9:15]}, self.final_depth,
+                self.final_segmentation)
             info["_final_observation"] = done
         if self.is_goal:
             info["TimeLimit.truncated"] = self.truncated
@@ -383,7 +400,8 @@ class SO100VecEnv:
         if self.autoreset:
             self.final_obs.copy_(self.obs)
             self._mask.copy_(done)
-            self.renderer.render(out=self.final_pixels, mask=self._mask)
+            self.renderer.render(out=self.final_pixels, mask=self._mask, depth=self.final_depth,
+                                 segmentation=self.final_segmentation)
             _native.check(self.lib.so100_reset(self._handle, ctypes.byref(self._buf), _native.ptr(self._mask), None,
                                                s), "so100_reset")
             if self._visual is not None and self._visual[1]:
@@ -397,6 +415,15 @@ class SO100VecEnv:
         self.renderer.render(flat=self.pixels_flat)
         if self.pixels_flat is not None:
             self.pixels_flat[:, self._npix:].copy_(self.obs[:, 9:15])
+
+    @staticmethod
+    def _with_aux(obs, depth, segmentation):
+        """obs with the "depth" / "segmentation" keys of the options that are on"""
+        if depth is not None:
+            obs["depth"] = depth
+        if segmentation is not None:
+            obs["segmentation"] = segmentation
+        return obs
 
     def episode_statistics(self, clear=False):
         """Totals of the episodes finished since construction (or the last ``clear``), reduced over the envs
@@ -420,12 +447,13 @@ class SO100VecEnv:
             agent_pos = self.obs[:, 9:15]                       # qpos[:6] float32 (single_arm.py:45-50)
             if self.is_goal:                                     # _flatten_observation (env.py:267-270)
                 if self.pixels_flat is not None:
-                    return {"observation": self.pixels_flat, "achieved_goal": self.achieved_goal,
-                            "desired_goal": self.desired_goal}
+                    return self._with_aux({"observation": self.pixels_flat, "achieved_goal": self.achieved_goal,
+                                           "desired_goal": self.desired_goal}, self.depth, self.segmentation)
                 flat = self.pixels.reshape(self.num_envs, -1).to(_torch().float32).div_(255.0)
-                return {"observation": _torch().cat([flat, agent_pos], dim=1), "achieved_goal": self.achieved_goal,
-                        "desired_goal": self.desired_goal}
-            return {"pixels": self.pixels, "agent_pos": agent_pos}
+                return self._with_aux({"observation": _torch().cat([flat, agent_pos], dim=1),
+                                       "achieved_goal": self.achieved_goal, "desired_goal": self.desired_goal},
+                                      self.depth, self.segmentation)
+            return self._with_aux({"pixels": self.pixels, "agent_pos": agent_pos}, self.depth, self.segmentation)
         if self.is_goal:
             return {"observation": self.obs, "achieved_goal": self.achieved_goal, "desired_goal": self.desired_goal}
         return self.obs

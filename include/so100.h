@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SO100_ABI_VERSION 20  /* 20: so100_view / so100_render_views / so100_render_materials / so100_views_sample / so100_view_bytes (camera, lights and colours per env);  19: so100_render_to / so100_image_out (one render launch, several sinks: hwc, chw, flat float32);  18: env packing of the fused step (so100_set_env_packing, so100_env_packing, so100_env_order, so100_env_cost, so100_wave_cost);  17: so100_pool_stats (the fused step's contact-record pool, sized never to run out);  16: so100_source_hash;  15: the EE variant's mocap marker box collides (SO100_NGEOM 16, SO100_NPAIR 209, SO100_NCON_MAX 643, debug stride 3,922);  14: no per-env contact cap (SO100_NCON_MAX: every pair at its collider's maximum), debug stride 3,436 (SO100_DBG_OVF), ncon_dropped always 0, status -3 for a caught C++ exception;  13: so100_buffers.ep_return / ep_final / ep_accum (device-side episode statistics);  12: so100_model.convex (GJK/EPA mesh collider, MuJoCo 3.3.3 default), box-box up to 8 contacts, cube-table one convex contact;  11: so100_buffers.ncon_dropped, debug stride 160 (contact friction forces), so100_set_fused_build;  10: so100_hull_cells (MPR support lookup);  9: pad/link-hull pairs (SO100_NPAIR 191);  8: fused step kernel, so100_set_step_mode;  7: reward64 buffer;  6: Base hull + pad pairs (SO100_NPAIR 155, SO100_NHULL_ALL 10); 5: EE/mocap weld, render API */
+#define SO100_ABI_VERSION 21  /* 21: so100_render_aux / so100_aux_out / so100_render_labels / so100_aux_out_bytes (depth and segmentation images from the render launch);  20: so100_view / so100_render_views / so100_render_materials / so100_views_sample / so100_view_bytes (camera, lights and colours per env);  19: so100_render_to / so100_image_out (one render launch, several sinks: hwc, chw, flat float32);  18: env packing of the fused step (so100_set_env_packing, so100_env_packing, so100_env_order, so100_env_cost, so100_wave_cost);  17: so100_pool_stats (the fused step's contact-record pool, sized never to run out);  16: so100_source_hash;  15: the EE variant's mocap marker box collides (SO100_NGEOM 16, SO100_NPAIR 209, SO100_NCON_MAX 643, debug stride 3,922);  14: no per-env contact cap (SO100_NCON_MAX: every pair at its collider's maximum), debug stride 3,436 (SO100_DBG_OVF), ncon_dropped always 0, status -3 for a caught C++ exception;  13: so100_buffers.ep_return / ep_final / ep_accum (device-side episode statistics);  12: so100_model.convex (GJK/EPA mesh collider, MuJoCo 3.3.3 default), box-box up to 8 contacts, cube-table one convex contact;  11: so100_buffers.ncon_dropped, debug stride 160 (contact friction forces), so100_set_fused_build;  10: so100_hull_cells (MPR support lookup);  9: pad/link-hull pairs (SO100_NPAIR 191);  8: fused step kernel, so100_set_step_mode;  7: reward64 buffer;  6: Base hull + pad pairs (SO100_NPAIR 155, SO100_NHULL_ALL 10); 5: EE/mocap weld, render API */
 
 /* tasks (gym_so100/__init__.py:4-32 ids; single_arm.py task classes) */
 #define SO100_TASK_CUBE_TO_BIN 0          /* gym_so100/SO100CubeToBin-v0, TimeLimit 700 */
@@ -297,6 +297,28 @@ typedef struct so100_view_dr {
  * = 0.  Enqueued on stream. */
 int so100_views_sample(so100_env* env, const so100_view_dr* dr, const so100_camera* cam, const uint32_t* base_rgb,
                        const uint32_t* episode, const uint8_t* mask, so100_view* views, void* stream);
+
+/* ---- (ABI 21) depth and segmentation images (dm_control's physics.render(depth=True / segmentation=True)), written by
+ * the render launch itself: the kernel's per-pixel key is depth bits << 32 | RGB8 << 8 | label, so the nearest surface
+ * wins, equal depths take the smaller packed RGB (the colour images are so100_render_to's / so100_render_views' bit
+ * for bit) and equal colours the smaller label.  DESIGN.md §3.7. */
+/* labels: host [ntri] bytes, each < 255, for the mesh of the last so100_render_mesh call (a new mesh drops them) */
+int so100_render_labels(so100_env* env, const uint8_t* label, int ntri);
+typedef struct so100_aux_out {
+  uint32_t size;     /* sizeof(so100_aux_out): the callee rejects a mismatch */
+  float*   depth;    /* [n][H][W] or NULL; background 0.0f */
+  uint8_t* label;    /* [n][H][W] or NULL; background 255 */
+} so100_aux_out;
+int so100_aux_out_bytes(void);
+/* so100_render_to / so100_render_views (views may be NULL) with the further sinks of aux; out may be NULL.  depth is
+ * the float32 the depth test compared: the distance along the camera's viewing axis in metres (not the ray length).
+ * label is the winning triangle's uploaded byte.  No alignment is asked of label; depth must be 4-byte aligned, as a
+ * float pointer is.  A masked-out env is untouched in every sink.  Nonzero (text in so100_last_error) for a NULL env, a
+ * wrong `size` in either struct, no sink at all across both, a label sink without uploaded labels, views without
+ * uploaded materials, and for what so100_render_to rejects. */
+int so100_render_aux(so100_env* env, const float* qpos, const uint8_t* mask, const so100_camera* cam,
+                     const so100_view* views, int width, int height, const so100_image_out* out,
+                     const so100_aux_out* aux, void* stream);
 
 /* Batched sparse GoalEnv reward (env.py:341-353): out[i] = ||a_i - d_i|| < threshold ? 0 : -1. */
 int so100_goal_reward(so100_env* env, int n, const float* achieved, const float* desired, float* out,
