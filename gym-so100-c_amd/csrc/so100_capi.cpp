@@ -35,6 +35,9 @@ hipError_t launch_render_views(const DevModel*, const float4*, const int*, const
 hipError_t launch_render_aux(const DevModel*, const float4*, const int*, const uint32_t*, const uint8_t*, const uint8_t*,
                              int, const float*, const uint8_t*, const so100_camera&, const so100_view*, int, int, int,
                              const so100_image_out&, const so100_aux_out&, hipStream_t);
+hipError_t launch_render_cams(const DevModel*, const float4*, const int*, const uint32_t*, const uint8_t*, const uint8_t*,
+                              int, const float*, const uint8_t*, const so100_cams&, const so100_view*, int, int, int,
+                              const so100_image_out&, const so100_aux_out&, hipStream_t);
 hipError_t launch_views_sample(const so100_view_dr&, const so100_camera&, const uint32_t*, const uint32_t*,
                                const uint8_t*, so100_view*, int, int, hipStream_t);
 hipError_t alloc_workspace(int, Workspace*);
@@ -1339,6 +1342,61 @@ static int so100_render_aux_impl(so100_env* env, const float* qpos, const uint8_
                        aux ? aux : &no_aux);
 }
 
+// the launch over (env, camera): so100_render_aux's checks, per camera where they are the camera's
+static int so100_render_cams_impl(so100_env* env, const float* qpos, const uint8_t* mask, const so100_cams* cams,
+                                  const so100_view* views, int width, int height, const so100_image_out* out,
+                                  const so100_aux_out* aux, void* stream) {
+  // the structs' sizes first: nothing else of them is read before they are known to be this library's layout
+  if (cams && cams->size != sizeof(so100_cams))
+    return size_mismatch("so100_render_cams", "so100_cams", cams->size, sizeof(so100_cams));
+  if (out && out->size != sizeof(so100_image_out))
+    return size_mismatch("so100_render_cams", "so100_image_out", out->size, sizeof(so100_image_out));
+  if (aux && aux->size != sizeof(so100_aux_out))
+    return size_mismatch("so100_render_cams", "so100_aux_out", aux->size, sizeof(so100_aux_out));
+  if (!cams) return fail("so100_render_cams: NULL cams");
+  char msg[160];
+  if (cams->ncam < 1 || cams->ncam > SO100_MAX_CAMS) {
+    snprintf(msg, sizeof(msg), "so100_render_cams: ncam %d, expected 1..%d", cams->ncam, SO100_MAX_CAMS);
+    return fail(msg);
+  }
+  for (int c = 0; c < cams->ncam; c++)
+    if (cams->frame_body[c] < 0 || cams->frame_body[c] >= SO100_NBODY) {
+      snprintf(msg, sizeof(msg), "so100_render_cams: frame_body[%d] %d, expected 0 (world) or 1..%d", c,
+               cams->frame_body[c], SO100_NBODY - 1);
+      return fail(msg);
+    }
+  auto bad = [&](const char* what) {
+    snprintf(msg, sizeof(msg), "so100_render_cams: %s", what);
+    return fail(msg);
+  };
+  // what the arguments alone decide comes before the env is looked at
+  const int K = cams->ncam;
+  if (width <= 0 || height <= 0 || width > 4096 || (long)width * height * K > (1L << 22))
+    return bad("bad image size (width <= 4096, width*height*ncam <= 2^22)");
+  if (out && out->flat && out->flat_pitch < (int64_t)3 * width * height * K) return bad("flat_pitch < ncam*3*H*W");
+  if (!(out && (out->hwc || out->chw || out->flat)) && !(aux && (aux->depth || aux->label)))
+    return bad("no sink (hwc, chw, flat, depth and label are all NULL)");
+  if (!env) return bad("NULL env");
+  if (!qpos) return bad("bad arguments");
+  if (env->r_ntri <= 0) return bad("no render mesh (so100_render_mesh)");
+  for (int c = 0; c < K; c++) {
+    const so100_camera& cam = cams->cam[c];
+    if (cam.nlight < 0 || cam.nlight > SO100_MAX_LIGHTS || !(cam.fovy > 0.f && cam.fovy < 180.f)) {
+      snprintf(msg, sizeof(msg), "so100_render_cams: bad camera %d", c);
+      return fail(msg);
+    }
+  }
+  if (views && !env->r_mat) return bad("no materials (so100_render_materials)");
+  if (aux && aux->label && !env->r_label) return bad("no labels (so100_render_labels)");
+  const so100_image_out none{(uint32_t)sizeof(so100_image_out), nullptr, nullptr, nullptr, 0};
+  const so100_aux_out no_aux{(uint32_t)sizeof(so100_aux_out), nullptr, nullptr};
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_render_cams(env->d_model, env->r_tri, env->r_body, env->r_rgb, env->r_mat, env->r_label,
+                                           env->r_ntri, qpos, mask, *cams, views, env->n, width, height,
+                                           out ? *out : none, aux ? *aux : no_aux, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip("so100_render_cams", e);
+}
+
 static int so100_views_sample_impl(so100_env* env, const so100_view_dr* dr, const so100_camera* cam,
                                    const uint32_t* base_rgb, const uint32_t* episode, const uint8_t* mask,
                                    so100_view* views, void* stream) {
@@ -1398,6 +1456,18 @@ int so100_render_aux(so100_env* env, const float* qpos, const uint8_t* mask, con
     return so100_render_aux_impl(env, qpos, mask, cam, views, width, height, out, aux, stream);
   } catch (...) {
     return caught("so100_render_aux");
+  }
+}
+
+int so100_cams_bytes(void) { return (int)sizeof(so100_cams); }
+
+int so100_render_cams(so100_env* env, const float* qpos, const uint8_t* mask, const so100_cams* cams,
+                      const so100_view* views, int width, int height, const so100_image_out* out,
+                      const so100_aux_out* aux, void* stream) {
+  try {
+    return so100_render_cams_impl(env, qpos, mask, cams, views, width, height, out, aux, stream);
+  } catch (...) {
+    return caught("so100_render_cams");
   }
 }
 

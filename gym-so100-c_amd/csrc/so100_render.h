@@ -1,7 +1,8 @@
-// so100_render.h - the render kernel's body, shared by its four launches: so100_render.hip (the hwc image alone),
+// so100_render.h - the render kernel's body, shared by its five launches: so100_render.hip (the hwc image alone),
 // so100_render_sinks.hip (so100_render_to's further sinks), so100_render_views.hip (so100_render_views: camera,
-// lights and colours per env) and so100_render_aux.hip (so100_render_aux: the depth and label sinks, with or without
-// views).  One translation unit per kernel: with two instantiations in one unit the hwc-only kernel was scheduled
+// lights and colours per env), so100_render_aux.hip (so100_render_aux: the depth and label sinks, with or without
+// views) and so100_render_cams.hip (so100_render_cams: the aux launch over a grid of (env, camera), with cameras that
+// ride on a body).  One translation unit per kernel: with two instantiations in one unit the hwc-only kernel was scheduled
 // differently and measured slower.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -53,6 +54,14 @@ struct RenderAuxArgs : RenderViewArgs {
   float* depth;                         // [n][height][width] or null: 1 / izp of the winning key; background 0.0f
   uint8_t* seg;                         // [n][height][width] or null: the winning key's label; background 255
 };
+// the launch over (env, camera) (so100_render_cams): block (env, c) is the aux kernel's block drawing env from cams[c]
+// and views[c * n + env] into slot env * ncam + c of every sink; frame_body[c] > 0 puts cams[c] (and its records) in
+// that body's frame.  a.cam is not read
+struct RenderCamsArgs : RenderAuxArgs {
+  int ncam;
+  so100_camera cams[SO100_MAX_CAMS];
+  int frame_body[SO100_MAX_CAMS];       // 0 world, 1..8 the body the camera is mounted on
+};
 constexpr int kViewWords = (int)(sizeof(so100_view) / sizeof(uint32_t));
 static_assert(sizeof(so100_view) == 160 && kViewWords == 40, "so100_view: 40 dwords");
 // the env's record in LDS, filled one dword per thread
@@ -102,19 +111,29 @@ DEV uint32_t shade(const Cam& c, int nlight, const float* cm, const float* p0, c
 // the camera-like record the body reads: a.cam, or with views the env's record in LDS
 template <class Args>
 DEV decltype(auto) view_source(const Args& a, const ViewLds& vl) {
-  if constexpr (std::is_same<Args, RenderViewArgs>::value || std::is_same<Args, RenderAuxArgs>::value) return (vl.v);
+  if constexpr (std::is_same<Args, RenderViewArgs>::value || std::is_same<Args, RenderAuxArgs>::value ||
+                std::is_same<Args, RenderCamsArgs>::value)
+    return (vl.v);
   else return (a.cam);
+}
+// the launch's camera: the block's own of RenderCamsArgs, a.cam in the other four
+template <class Args>
+DEV const so100_camera& launch_cam(const Args& a) {
+  if constexpr (std::is_same<Args, RenderCamsArgs>::value) return a.cams[blockIdx.y];
+  else return a.cam;
 }
 
 // Args = RenderArgs: the hwc image alone (so100_render and every hwc-only so100_render_to);
 // Args = RenderSinkArgs: every non-null sink of a.out / a.chw / a.flat is written from the same band;
 // Args = RenderViewArgs: the same sinks, drawn from views[env] (not referenced, vl costs the other two no LDS);
-// Args = RenderAuxArgs: those sinks and a.depth / a.seg, from views[env] or (a.views null) from a.cam through vl.
+// Args = RenderAuxArgs: those sinks and a.depth / a.seg, from views[env] or (a.views null) from a.cam through vl;
+// Args = RenderCamsArgs: the aux kernel's block per (env, camera): grid (n, ncam), see the struct.
 template <class Args>
 __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
   constexpr bool kSinks = sizeof(Args) != sizeof(RenderArgs);
   constexpr bool kView = std::is_same<Args, RenderViewArgs>::value;
-  constexpr bool kAux = std::is_same<Args, RenderAuxArgs>::value;
+  constexpr bool kCams = std::is_same<Args, RenderCamsArgs>::value;
+  constexpr bool kAux = std::is_same<Args, RenderAuxArgs>::value || kCams;
   constexpr int kColShift = kAux ? 8 : 0;                  // the colour's place in the key's lower half
   __shared__ ViewLds vl;
   __shared__ EnvShared sh;
@@ -127,26 +146,30 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
   const int tid = threadIdx.x, env = blockIdx.x;
   if (env >= a.n || (a.mask && !a.mask[env])) return;     // uniform per block
   const int W = a.width, H = a.height;
+  const so100_camera& lc = launch_cam(a);
+  // the block's slot in every sink and its view record, evaluated where they are used: env in the other four kernels
+  auto slot = [&]() -> size_t { if constexpr (kCams) return (size_t)env * a.ncam + blockIdx.y; else return (size_t)env; };
+  auto vrec = [&]() -> size_t { if constexpr (kCams) return (size_t)blockIdx.y * a.n + env; else return (size_t)env; };
 
   // ---- forward kinematics of this env (the stage kernel's fk_stage on thread 0)
   if (tid < SO100_NQ) sh.qpos[tid] = a.qpos[(size_t)env * SO100_NQ + tid];
   if constexpr (kView) {
-    if (tid < kViewWords) vl.w[tid] = reinterpret_cast<const uint32_t*>(a.views + env)[tid];
+    if (tid < kViewWords) vl.w[tid] = reinterpret_cast<const uint32_t*>(a.views + vrec())[tid];
   }
   if constexpr (kAux) {
     if (a.views) {                                         // uniform per launch
-      if (tid < kViewWords) vl.w[tid] = reinterpret_cast<const uint32_t*>(a.views + env)[tid];
+      if (tid < kViewWords) vl.w[tid] = reinterpret_cast<const uint32_t*>(a.views + vrec())[tid];
     } else if (tid == 0) {
       // the base camera as a record (what an identity record holds, bit for bit); rgb is not read without views
       so100_view& v = vl.v;
-      for (int k = 0; k < 3; k++) v.pos[k] = a.cam.pos[k];
-      for (int k = 0; k < 9; k++) v.mat[k] = a.cam.mat[k];
-      v.fovy = a.cam.fovy;
-      v.head_ambient = a.cam.head_ambient;
-      v.head_diffuse = a.cam.head_diffuse;
+      for (int k = 0; k < 3; k++) v.pos[k] = lc.pos[k];
+      for (int k = 0; k < 9; k++) v.mat[k] = lc.mat[k];
+      v.fovy = lc.fovy;
+      v.head_ambient = lc.head_ambient;
+      v.head_diffuse = lc.head_diffuse;
       for (int l = 0; l < SO100_MAX_LIGHTS; l++) {
-        v.light_diffuse[l] = a.cam.light_diffuse[l];
-        for (int k = 0; k < 3; k++) v.light_dir[l][k] = a.cam.light_dir[l][k];
+        v.light_diffuse[l] = lc.light_diffuse[l];
+        for (int k = 0; k < 3; k++) v.light_dir[l][k] = lc.light_dir[l][k];
       }
     }
   }
@@ -173,7 +196,24 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
       for (int k = 0; k < 9; k++) frm[b][k] = R[k];
       for (int k = 0; k < 3; k++) frm[b][9 + k] = P[k];
     }
-    if (a.cam.track) {
+    if constexpr (kCams) {
+      // a camera on a body: pos (and mat) are in the body's frame.  The record's pos becomes the world position here,
+      // before the barrier after which the other threads read it; a world camera (0) is not transformed at all
+      const int fb = a.frame_body[blockIdx.y];
+      if (fb > 0) {
+        const float* F = frm[fb];
+        const float p[3] = {vl.v.pos[0], vl.v.pos[1], vl.v.pos[2]};
+        for (int k = 0; k < 3; k++) vl.v.pos[k] = F[3 * k] * p[0] + F[3 * k + 1] * p[1] + F[3 * k + 2] * p[2] + F[9 + k];
+        if (!lc.track) {                                   // a rigid mount: cmat = R_b . mat
+          float mm[9];
+          for (int k = 0; k < 9; k++) mm[k] = vl.v.mat[k];
+          for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++)
+              vl.v.mat[3 * i + j] = F[3 * i] * mm[j] + F[3 * i + 1] * mm[3 + j] + F[3 * i + 2] * mm[6 + j];
+        }
+      }
+    }
+    if (lc.track) {
       // mode="targetbody" on the ee body (scene_so100.xml:30 front_close -> vx300s_left/camera_focus, whose
       // origin is ee_site): MuJoCo's mj_camlight frame z = pos - target, x = (0,0,1) x z, y = z x x
       float z[3] = {cv.pos[0] - sh.site_ee[0], cv.pos[1] - sh.site_ee[1], cv.pos[2] - sh.site_ee[2]};
@@ -195,7 +235,7 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
   const float th = tanf(0.5f * cv.fovy * 0.017453292519943295f);
   const float aspect = (float)W / (float)H;
   const int band = kTilePx / W > 0 ? kTilePx / W : 1;        // rows per band
-  uint8_t* img = a.out + (size_t)env * H * W * 3;              // used where a.out is not null
+  uint8_t* img = a.out + slot() * H * W * 3;              // used where a.out is not null
 
   for (int y0 = 0; y0 < H; y0 += band) {
     const int y1 = min(H, y0 + band);
@@ -223,7 +263,7 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
         const float cy = cmat[1] * d[0] + cmat[4] * d[1] + cmat[7] * d[2];
         const float cz = cmat[2] * d[0] + cmat[5] * d[1] + cmat[8] * d[2];
         const float depth = -cz;
-        ok = ok && depth > a.cam.znear;
+        ok = ok && depth > lc.znear;
         const float id = 1.f / depth;
         sx[v] = (cx * id / (th * aspect) * 0.5f + 0.5f) * (float)W;
         sy[v] = (0.5f - cy * id / th * 0.5f) * (float)H;
@@ -243,7 +283,7 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
       if constexpr (kView) base = cv.rgb[a.material[t]];
       else if constexpr (kAux) base = a.views ? cv.rgb[a.material[t]] : a.tri_rgb[t];
       else base = a.tri_rgb[t];
-      col = shade(cv, a.cam.nlight, cmat, pw[0], pw[1], pw[2], base);
+      col = shade(cv, lc.nlight, cmat, pw[0], pw[1], pw[2], base);
       if constexpr (kAux) col = (col << 8) | (a.label ? (uint32_t)a.label[t] : 0u);   // the key's lower half
       return true;
     };
@@ -319,7 +359,7 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
         // nothing outside the span is touched (its neighbours are other planes, other envs or the caller's memory)
 #pragma unroll 1
         for (int c = 0; c < 3; c++) {
-          uint8_t* p = a.chw + (((size_t)env * 3 + c) * H + y0) * W;
+          uint8_t* p = a.chw + ((slot() * 3 + c) * H + y0) * W;
           const int head = min(npx, (int)((4u - (uint32_t)((uintptr_t)p & 3u)) & 3u));
           const int nquad = (npx - head) >> 2;
           const int tail = head + 4 * nquad;
@@ -336,6 +376,7 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
         // float j of the band = byte j of its hwc form: consecutive threads store consecutive floats
         static constexpr ByteUnit kByteUnit{};
         float* f = a.flat + (size_t)env * (size_t)a.flat_pitch + (size_t)y0 * W * 3;
+        if constexpr (kCams) f += (size_t)blockIdx.y * 3 * H * W;      // camera c's floats within the env's row
         for (int j = tid; j < 3 * npx; j += kRenderThreads) {
           const int i = j / 3;
           f[j] = kByteUnit.v[chan(i, j - 3 * i)];
@@ -344,7 +385,7 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
       if constexpr (kAux) {
         if (a.depth) {
           // the float32 the depth test compared: the key's upper half as it is (the empty key gives 0.0f)
-          float* d = a.depth + ((size_t)env * H + y0) * W;
+          float* d = a.depth + (slot() * H + y0) * W;
           for (int i = tid; i < npx; i += kRenderThreads) {
             const unsigned long long key = zb[i];
             d[i] = key == ~0ull ? 0.f : __uint_as_float((uint32_t)(key >> 32));
@@ -353,7 +394,7 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
         if (a.seg) {
           // the key's low byte (the empty key's is 255, the background label); the chw plane's head / dword / tail
           // scheme on the band's span [p, p + npx): nothing outside it is touched
-          uint8_t* p = a.seg + ((size_t)env * H + y0) * W;
+          uint8_t* p = a.seg + (slot() * H + y0) * W;
           const int head = min(npx, (int)((4u - (uint32_t)((uintptr_t)p & 3u)) & 3u));
           const int nquad = (npx - head) >> 2;
           const int tail = head + 4 * nquad;

@@ -57,6 +57,25 @@ class SO100AuxOut(ctypes.Structure):
         super().__init__(ctypes.sizeof(SO100AuxOut), depth, label)
 
 
+SO100_MAX_CAMS = 4
+
+
+class SO100Cams(ctypes.Structure):
+    """Mirror of ``so100_cams`` (include/so100.h): the cameras of one ``so100_render_cams`` launch and the body each
+    rides on (0 = fixed in the world).  ``size`` is set to the mirror's size, which the callee checks against its own."""
+    _fields_ = [("size", ctypes.c_uint32), ("ncam", ctypes.c_int32), ("cam", SO100Camera * SO100_MAX_CAMS),
+                ("frame_body", ctypes.c_int32 * SO100_MAX_CAMS)]
+
+    def __init__(self, cams=(), frame_body=()):
+        super().__init__()
+        self.size = ctypes.sizeof(SO100Cams)
+        self.ncam = len(cams)
+        for c, cam in enumerate(cams[:SO100_MAX_CAMS]):
+            ctypes.memmove(ctypes.byref(self.cam[c]), ctypes.byref(cam), ctypes.sizeof(SO100Camera))
+        for c, b in enumerate(frame_body[:SO100_MAX_CAMS]):
+            self.frame_body[c] = int(b)
+
+
 SO100_NMATERIAL = 5
 
 
@@ -98,7 +117,7 @@ class NativeLibraryError(RuntimeError):
 _lib = None
 
 
-ABI_VERSION = 21         # include/so100.h SO100_ABI_VERSION
+ABI_VERSION = 22         # include/so100.h SO100_ABI_VERSION
 HULL_CELLG = 8           # SO100_HULL_CELLG
 HULL_NCELL = 6 * HULL_CELLG * HULL_CELLG
 
@@ -148,6 +167,9 @@ def load():
     lib.so100_render_labels.argtypes = [_P, _P, ctypes.c_int]
     lib.so100_render_aux.argtypes = [_P, _P, _P, ctypes.POINTER(SO100Camera), _P, ctypes.c_int, ctypes.c_int,
                                      ctypes.POINTER(SO100ImageOut), ctypes.POINTER(SO100AuxOut), _P]
+    lib.so100_cams_bytes.argtypes = []
+    lib.so100_render_cams.argtypes = [_P, _P, _P, ctypes.POINTER(SO100Cams), _P, ctypes.c_int, ctypes.c_int,
+                                      ctypes.POINTER(SO100ImageOut), ctypes.POINTER(SO100AuxOut), _P]
     lib.so100_hull_cells.argtypes = [_P, _P, _P, ctypes.c_int]
     lib.so100_set_fused_build.argtypes = [_P, ctypes.c_int]
     lib.so100_fused_build.argtypes = [_P, ctypes.c_int]
@@ -163,7 +185,7 @@ def load():
                "so100_set_fused_build", "so100_fused_build", "so100_set_env_packing", "so100_env_packing",
                "so100_env_order", "so100_env_cost", "so100_wave_cost", "so100_view_bytes", "so100_render_materials",
                "so100_render_views", "so100_views_sample", "so100_aux_out_bytes", "so100_render_labels",
-               "so100_render_aux"):
+               "so100_render_aux", "so100_cams_bytes", "so100_render_cams"):
         getattr(lib, fn).restype = ctypes.c_int
     lib.so100_struct_sizes.argtypes = [_P, _P]
     lib.so100_struct_sizes.restype = ctypes.c_int
@@ -181,6 +203,9 @@ def load():
     if lib.so100_aux_out_bytes() != ctypes.sizeof(SO100AuxOut):
         raise NativeLibraryError(f"struct layout mismatch: so100_aux_out {lib.so100_aux_out_bytes()} vs "
                                  f"{ctypes.sizeof(SO100AuxOut)}")
+    if lib.so100_cams_bytes() != ctypes.sizeof(SO100Cams):
+        raise NativeLibraryError(f"struct layout mismatch: so100_cams {lib.so100_cams_bytes()} vs "
+                                 f"{ctypes.sizeof(SO100Cams)}")
     _lib = lib
     return lib
 
@@ -194,7 +219,7 @@ EXPORTED_SYMBOLS = ("so100_abi_version", "so100_last_error", "so100_source_hash"
                     "so100_fused_build", "so100_set_env_packing", "so100_env_packing", "so100_env_order",
                     "so100_env_cost", "so100_wave_cost", "so100_view_bytes", "so100_render_materials",
                     "so100_render_views", "so100_views_sample", "so100_aux_out_bytes", "so100_render_labels",
-                    "so100_render_aux")
+                    "so100_render_aux", "so100_cams_bytes", "so100_render_cams")
 
 
 def source_hash():

@@ -18,6 +18,11 @@ along the camera's viewing axis, background 0) and ``segmentation`` (uint8 [N, H
 background ``SEG_BACKGROUND``), what dm_control's ``physics.render(depth=True / segmentation=True)`` returns, written by
 the launch that draws the colour image (C-ABI ``so100_render_aux``).
 
+Several cameras: ``MultiCameraRenderer`` draws K <= 4 cameras of every env in one launch whose grid is (env, camera)
+(C-ABI ``so100_render_cams``): the reference task's ``top``, ``angle`` and ``front_close`` (tasks/single_arm.py:88-102)
+and cameras that ride on a body, such as the arm's own ``left_wrist`` on Fixed_Jaw (so_arm100.xml:126).  ``pixels`` is
+[N, K, H, W, 3] (or [N, K, 3, H, W]), depth and segmentation [N, K, H, W], view records [K, N, 40].
+
 It is a rasteriser of its own, not MuJoCo's OpenGL pipeline: geometry and colours are the scene's, the
 pixel values are not MuJoCo's (no specular, shadows, fog or anti-aliasing).
 """
@@ -31,6 +36,12 @@ from . import _native
 ASSET = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets", "so100_render.npz")
 CAMERAS = ("top", "angle", "left_pillar", "right_pillar", "front_close")
 TRACKING = ("front_close",)              # mode="targetbody" on the ee body: frame per env
+# cameras mounted on a body (so100_cams.frame_body): name -> body, position in the body's frame, fovy, tracking.
+# left_wrist: so_arm100.xml:126, <camera name="left_wrist" pos="0 .0 0.55" fovy="20" mode="targetbody"
+# target="vx300s_left/camera_focus"/> in body Fixed_Jaw (body 6 of 0 world, 1 Base, 2..7 the arm's links, 8 cube)
+MOUNTED_CAMERAS = ("left_wrist",)
+_MOUNTED = {"left_wrist": dict(body=6, pos=(0.0, 0.0, 0.55), fovy=20.0)}
+NBODY = 9
 ZNEAR = 0.01
 MATERIALS = ("table", "bin", "arm_light", "arm_dark", "cube")      # SO100_NMATERIAL ids 0..4 (include/so100.h)
 # segmentation classes (segment_labels): label k is SEG_CLASSES[k], a pixel no triangle covers is SEG_BACKGROUND
@@ -70,6 +81,69 @@ def make_camera(scene, name="top"):
         cam.light_dir[i][:] = [float(x) for x in scene["light_dir"][i]]
         cam.light_diffuse[i] = float(scene["light_diffuse"][i])
     return cam
+
+
+def make_mounted_camera(scene, body, pos, mat=None, fovy=None):
+    """so100_camera riding on ``body`` (1 Base, 2..7 the arm's links, 8 the cube) under the scene's lights: ``pos`` is in
+    the body's frame.  With ``mat`` ([3,3], columns = camera x right, y up, z backward, in the body's frame) it is a rigid
+    mount; with mat=None it tracks the ee body from its moving position (mode="targetbody", as left_wrist does).  The
+    body rides in the camera's ``frame_body`` attribute, which MultiCameraRenderer reads (a world camera has none)."""
+    body = int(body)
+    if not 1 <= body < NBODY:
+        raise ValueError(f"body {body}: a mounted camera rides on body 1..{NBODY - 1}")
+    cam = make_camera(scene, "top")                      # the scene's lights, headlight and znear
+    cam.pos[:] = [float(x) for x in pos]
+    if mat is None:
+        cam.track = 1
+        cam.mat[:] = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0]
+    else:
+        m = np.asarray(mat, dtype=np.float64)
+        if m.shape != (3, 3):
+            raise ValueError("mat: a [3, 3] rotation in the body's frame")
+        cam.track = 0
+        cam.mat[:] = [float(x) for x in m.reshape(-1)]
+    if fovy is not None:
+        cam.fovy = float(fovy)
+    if not 0.0 < cam.fovy < 180.0:
+        raise ValueError(f"fovy {cam.fovy}: degrees in (0, 180)")
+    cam.frame_body = body
+    return cam
+
+
+def camera_by_name(scene, name):
+    """so100_camera of a name in CAMERAS (fixed in the world) or MOUNTED_CAMERAS (frame_body set)."""
+    if name in _MOUNTED:
+        return make_mounted_camera(scene, **_MOUNTED[name])
+    if name not in CAMERAS:
+        raise ValueError(f"camera {name!r}: one of {CAMERAS + MOUNTED_CAMERAS}")
+    return make_camera(scene, name)
+
+
+def check_camera_names(cameras):
+    """The argument check of a ``cameras=`` tuple (no device use): 1..SO100_MAX_CAMS known names.  Returns the tuple."""
+    if isinstance(cameras, str):
+        raise ValueError("cameras: a tuple of camera names, e.g. ('top', 'left_wrist')")
+    names = tuple(cameras)
+    if not 1 <= len(names) <= _native.SO100_MAX_CAMS:
+        raise ValueError(f"cameras: 1..{_native.SO100_MAX_CAMS} cameras, got {len(names)}")
+    for c in names:
+        if not isinstance(c, _native.SO100Camera) and c not in CAMERAS + MOUNTED_CAMERAS:
+            raise ValueError(f"camera {c!r}: one of {CAMERAS + MOUNTED_CAMERAS}")
+    return names
+
+
+def camera_seed(seed, c):
+    """The seed of camera c's view records: the given seed for camera 0 (one camera reproduces CameraRenderer's
+    records), else splitmix64(seed + c * 0x9E3779B97F4A7C15 mod 2^64)."""
+    x = int(seed) & 0xFFFFFFFFFFFFFFFF
+    if c == 0:
+        return x
+    M = 0xFFFFFFFFFFFFFFFF
+    x = (x + c * 0x9E3779B97F4A7C15) & M
+    x = (x + 0x9E3779B97F4A7C15) & M
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & M
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & M
+    return x ^ (x >> 31)
 
 
 def material_ids(scene):
@@ -313,4 +387,128 @@ class CameraRenderer:
         _native.check(v.lib.so100_render_to(v._handle, _native.ptr(q), _native.ptr(m), ctypes.byref(self.camera),
                                             self.width, self.height, ctypes.byref(sinks), v._stream()),
                       "so100_render_to")
+        return o
+
+
+class MultiCameraRenderer:
+    """Renders every env of ``venv`` from K <= 4 cameras with one HIP launch per call (C-ABI ``so100_render_cams``, grid
+    (env, camera)) into persistent tensors with the camera axis after the env's.
+
+    cameras: names of CAMERAS / MOUNTED_CAMERAS, or so100_camera structs (make_camera, make_mounted_camera).
+    ``pixels`` is uint8 [N,K,H,W,3], with channels_first [N,K,3,H,W] (its free reshape [N,3K,H,W] is the channel-stacked
+    image a CNN takes); ``depth`` float32 and ``segmentation`` uint8 are [N,K,H,W]; ``views`` is [K,N,40], camera-major,
+    so that each camera's records are the contiguous [N,40] array so100_views_sample fills.  A mounted camera's records
+    hold pos (and mat) in its body's frame: camera jitter is then a mount tolerance."""
+
+    def __init__(self, venv, width=640, height=480, cameras=("top", "angle", "front_close"), channels_first=False,
+                 depth=False, segmentation=False):
+        torch = _torch()
+        self.venv = venv
+        self.width, self.height = int(width), int(height)
+        names = check_camera_names(cameras)
+        K = self.ncam = len(names)
+        if not (0 < self.width <= 4096 and 0 < self.height and self.width * self.height * K <= 1 << 22):
+            raise ValueError(f"image {self.width}x{self.height} x {K} cameras: width <= 4096 and "
+                             f"width*height*cameras <= 2^22")
+        scene = load_scene()
+        tri = np.ascontiguousarray(scene["tri"], dtype=np.float32)
+        body = np.ascontiguousarray(scene["body"], dtype=np.int32)
+        rgb = np.ascontiguousarray(scene["rgb"], dtype=np.float32)
+        _native.check(venv.lib.so100_render_mesh(venv._handle, tri.ctypes.data, body.ctypes.data, rgb.ctypes.data,
+                                                 len(body)), "so100_render_mesh")
+        mat, base = material_ids(scene)
+        _native.check(venv.lib.so100_render_materials(venv._handle, mat.ctypes.data, len(mat)),
+                      "so100_render_materials")
+        self.base_rgb = np.ascontiguousarray(pack_rgb8(base), dtype=np.uint32)
+        lab, _ = segment_labels(scene)
+        _native.check(venv.lib.so100_render_labels(venv._handle, lab.ctypes.data, len(lab)), "so100_render_labels")
+        self.camera_names = tuple(c if isinstance(c, str) else f"camera{k}" for k, c in enumerate(names))
+        self.cameras = [camera_by_name(scene, c) if isinstance(c, str) else c for c in names]
+        self.frame_body = tuple(int(getattr(c, "frame_body", 0)) for c in self.cameras)
+        self.cams = _native.SO100Cams(self.cameras, self.frame_body)
+        self.views = None                # [K, N, 40] int32 device tensor of so100_view records, or None
+        self.ntri = len(body)
+        self.channels_first = bool(channels_first)
+        self.image_shape = (K, 3, self.height, self.width) if self.channels_first else (K, self.height, self.width, 3)
+        n, d = venv.num_envs, venv.device
+        self.pixels = torch.zeros(n, *self.image_shape, dtype=torch.uint8, device=d)
+        self.depth = torch.zeros(n, K, self.height, self.width, dtype=torch.float32, device=d) if depth else None
+        self.segmentation = torch.full((n, K, self.height, self.width), SEG_BACKGROUND, dtype=torch.uint8,
+                                       device=d) if segmentation else None
+
+    def identity_views(self):
+        """Set ``views`` to each camera's base view in every env: the images are then bit for bit those without
+        views.  Returns the tensor."""
+        return self.sample_views({}, 0)
+
+    def sample_views(self, ranges, seed, episode=None, mask=None):
+        """CameraRenderer.sample_views per camera: one so100_views_sample call on camera c's slice ``views[c]`` with
+        camera c as the base and the seed camera_seed(seed, c), so a record is a pure function of (seed, camera, global
+        env id, episode) and one camera reproduces CameraRenderer's records.  Allocates ``views`` on first use."""
+        torch = _torch()
+        v = self.venv
+        if episode is not None and (episode.shape != (v.num_envs,) or episode.dtype != torch.int32 or
+                                    episode.device != v.device or not episode.is_contiguous()):
+            raise ValueError("episode must be a contiguous int32 [N] tensor on the env's device")
+        m = None
+        if mask is not None:
+            if mask.shape != (v.num_envs,) or mask.device != v.device:
+                raise ValueError("mask must be an [N] tensor on the env's device")
+            m = mask.to(torch.uint8).contiguous()
+            self._view_mask_ref = m               # keep alive until the launches have run
+        if self.views is None:
+            self.views = torch.zeros(self.ncam, v.num_envs, _native.VIEW_WORDS, dtype=torch.int32, device=v.device)
+        for c in range(self.ncam):
+            dr = view_ranges(ranges, camera_seed(seed, c))
+            _native.check(v.lib.so100_views_sample(v._handle, ctypes.byref(dr), ctypes.byref(self.cameras[c]),
+                                                   self.base_rgb.ctypes.data, _native.ptr(episode), _native.ptr(m),
+                                                   _native.ptr(self.views[c]), v._stream()), "so100_views_sample")
+        return self.views
+
+    def render(self, qpos=None, out=None, mask=None, flat=None, views=None, depth=None, segmentation=None):
+        """Enqueue the one launch that draws qpos (default: the env's state) from every camera into out (default
+        ``self.pixels``).  mask: [N] envs to draw, in all their cameras (the others keep every image and flat row).
+        flat: contiguous float32 [N, P >= K*3HW]: floats [c*3HW, (c+1)*3HW) of row i are camera c's [H,W,3] bytes / 255.
+        views: [K, N, 40] records (default ``self.views``).  depth, segmentation: [N, K, H, W] (defaults the
+        renderer's own)."""
+        torch = _torch()
+        v = self.venv
+        K, H, W = self.ncam, self.height, self.width
+        q = v.qpos if qpos is None else qpos
+        o = self.pixels if out is None else out
+        if q.shape != (v.num_envs, v.qpos.shape[1]) or q.dtype != torch.float32 or not q.is_contiguous():
+            raise ValueError("qpos must be a contiguous float32 [N, 13] device tensor")
+        if o.shape != (v.num_envs, *self.image_shape) or o.dtype != torch.uint8 or not o.is_contiguous():
+            raise ValueError("out must be a contiguous uint8 [N, K, %s] device tensor" %
+                             ("3, H, W" if self.channels_first else "H, W, 3"))
+        m = None
+        if mask is not None:
+            if mask.shape != (v.num_envs,) or mask.device != v.device:
+                raise ValueError("mask must be an [N] tensor on the env's device")
+            m = mask.to(torch.uint8).contiguous()
+            self._mask_ref = m                    # keep alive until the launch has run
+        vw = self.views if views is None else views
+        if vw is not None and (vw.shape != (K, v.num_envs, _native.VIEW_WORDS) or vw.element_size() != 4 or
+                               not vw.is_contiguous() or vw.device != o.device):
+            raise ValueError("views must be a contiguous 4-byte [K, N, 40] device tensor")
+        dp = self.depth if depth is None else depth
+        sg = self.segmentation if segmentation is None else segmentation
+        for t, dt, what in ((dp, torch.float32, "depth must be a contiguous float32"),
+                            (sg, torch.uint8, "segmentation must be a contiguous uint8")):
+            if t is not None and (t.shape != (v.num_envs, K, H, W) or t.dtype != dt or not t.is_contiguous() or
+                                  t.device != o.device):
+                raise ValueError(what + " [N, K, H, W] device tensor")
+        pitch = 0
+        if flat is not None:
+            if flat.dim() != 2 or flat.shape[0] != v.num_envs or flat.shape[1] < K * 3 * W * H or \
+                    flat.dtype != torch.float32 or not flat.is_contiguous() or flat.device != o.device:
+                raise ValueError("flat must be a contiguous float32 [N, P >= K*3*H*W] device tensor")
+            pitch = flat.shape[1]
+        sinks = _native.SO100ImageOut(hwc=None if self.channels_first else _native.ptr(o),
+                                      chw=_native.ptr(o) if self.channels_first else None,
+                                      flat=_native.ptr(flat), flat_pitch=pitch)
+        aux = _native.SO100AuxOut(depth=_native.ptr(dp), label=_native.ptr(sg))
+        _native.check(v.lib.so100_render_cams(v._handle, _native.ptr(q), _native.ptr(m), ctypes.byref(self.cams),
+                                              _native.ptr(vw), W, H, ctypes.byref(sinks), ctypes.byref(aux),
+                                              v._stream()), "so100_render_cams")
         return o

@@ -27,6 +27,10 @@ numpy interface requires.
 * the GoalEnv observes ``"observation"`` = the flattened image / 255 followed by agent_pos, float32 [3HW+6]
   (env.py:219-238, 267-270), filled on the device by the render launch (``SO100VecEnv(flat_pixels=True)``).
 
+``cameras=("top", "left_wrist")`` (K names of render.CAMERAS / render.MOUNTED_CAMERAS) observes K cameras drawn by one
+launch: the arm tasks, which then need ``channels_first=True``, emit ``pixels`` as uint8 [3K,H,W], the channel-stacked
+image SB3's CNN takes (a free reshape of the env's [N,K,3,H,W]); the GoalEnv emits float32 [K*3HW+6].
+
 The image (or flattened) tensor reaches the host by one asynchronous copy into pinned memory and one stream
 synchronisation per step.  Two pinned buffers alternate: **the image array of an observation returned by
 ``reset()`` / ``step()`` stays valid through the next ``step()`` and is overwritten by the one after it** (SB3's
@@ -56,12 +60,20 @@ class SO100SB3VecEnv(_VecEnvBase):
 
     def __init__(self, num_envs, task="so100_cube_to_bin", device="cuda:0", seed=0, max_episode_steps=None,
                  domain_randomization=None, env_offset=0, iterations=None, solver="newton", obs_type="so100_state",
-                 observation_width=640, observation_height=480, channels_first=False):
+                 observation_width=640, observation_height=480, channels_first=False, cameras=None):
         self.pixel_obs = obs_type == "so100_pixels_agent_pos"
         kw = {}
+        if cameras is not None:
+            if not self.pixel_obs:
+                raise ValueError("cameras need obs_type='so100_pixels_agent_pos'")
+            if task != "so100_goal" and not channels_first:
+                raise ValueError("cameras need channels_first=True: the K images are stacked along the channel axis, "
+                                 "[3K,H,W]")
         if self.pixel_obs:
             kw = dict(obs_type=obs_type, observation_width=observation_width, observation_height=observation_height,
                       channels_first=channels_first, flat_pixels=task == "so100_goal")
+            if cameras is not None:
+                kw["cameras"] = cameras
         elif obs_type != "so100_state":
             raise NotImplementedError(f"obs_type={obs_type!r}: 'so100_state' or 'so100_pixels_agent_pos'")
         elif channels_first:
@@ -78,6 +90,8 @@ class SO100SB3VecEnv(_VecEnvBase):
             import torch
             r = self.venv.renderer
             src = self.venv.pixels_flat if self.venv.is_goal else self.venv.pixels
+            if cameras is not None and not self.venv.is_goal:
+                src = src.view(n, -1, r.height, r.width)         # [N,K,3,H,W] as [N,3K,H,W]: no copy
             # the two pinned host buffers the image / flattened observation alternates between
             self._host = [torch.empty(src.shape, dtype=src.dtype, pin_memory=True) for _ in range(2)]
             self._host_i = 0
@@ -87,7 +101,7 @@ class SO100SB3VecEnv(_VecEnvBase):
                     "achieved_goal": goal_box, "desired_goal": goal_box})
             else:
                 obs_space = spaces.Dict({
-                    "pixels": spaces.Box(low=0, high=255, shape=tuple(r.image_shape), dtype=np.uint8),
+                    "pixels": spaces.Box(low=0, high=255, shape=tuple(src.shape[1:]), dtype=np.uint8),
                     "agent_pos": spaces.Box(low=-10.0, high=10.0, shape=(6,), dtype=np.float32)})
         elif self.venv.is_goal:
             obs_space = spaces.Dict({
@@ -152,6 +166,8 @@ class SO100SB3VecEnv(_VecEnvBase):
                 fgoal = _np(prev_goal[done_t])
             if self.pixel_obs:
                 fpix = _np(v.final_pixels[done_t])           # only the done envs' images, gathered on the device
+                if v.camera_names is not None and not v.is_goal:
+                    fpix = fpix.reshape(idx.size, *self._host[0].shape[1:])      # [K,3,H,W] as [3K,H,W]
                 if v.is_goal:                                # _flatten_observation (env.py:267-270), in numpy
                     fflat = np.concatenate([fpix.reshape(idx.size, -1).astype(np.float32) / np.float32(255.0),
                                             final[:, 9:15]], axis=1)
@@ -189,6 +205,8 @@ class SO100SB3VecEnv(_VecEnvBase):
         if not self.pixel_obs:
             return [None] * self.num_envs
         img = _np(self.venv.pixels)
+        if self.venv.camera_names is not None:               # several cameras: the first one's images
+            img = img[:, 0]
         if self.venv.channels_first:
             img = img.transpose(0, 2, 3, 1)
         return [img[i] for i in range(self.num_envs)]
@@ -241,7 +259,7 @@ class SO100SB3VecEnv(_VecEnvBase):
             big = "observation" if self.venv.is_goal else "pixels"
             host = self._host[self._host_i]
             self._host_i ^= 1
-            host.copy_(obs[big], non_blocking=True)
+            host.copy_(obs[big].view(host.shape), non_blocking=True)
             out = {k: _np(t) for k, t in obs.items() if k != big}
             torch.cuda.current_stream(self.venv.device).synchronize()
             out[big] = host.numpy()

@@ -116,13 +116,19 @@ class SO100VecEnv:
             ``final_segmentation`` ride in ``info["final_observation"]`` beside ``final_pixels``.  The GoalEnv's
             flattened ``"observation"`` stays as it is; the two tensors are further keys of its dict.  ValueError with
             any other obs_type.
+        cameras: None (default: the ``top`` camera, every call what it is without the argument) or a tuple of 1..4 names
+            of render.CAMERAS / render.MOUNTED_CAMERAS, e.g. ("top", "left_wrist"): pixel observations only (ValueError
+            otherwise).  ``pixels`` is then the one [N,K,H,W,3] tensor (channels_first: [N,K,3,H,W]) of K cameras drawn
+            by one launch (render.MultiCameraRenderer), ``camera_names`` names its K axis, ``depth`` / ``segmentation``
+            and the three ``final_*`` tensors gain the K axis, ``pixels_flat`` is [N, K*3HW+6] (camera c's image / 255
+            in floats [c*3HW, (c+1)*3HW), agent_pos last) and domain_randomization["visual"] draws a view per camera.
     """
 
     def __init__(self, num_envs, task="so100_cube_to_bin", obs_type="so100_state", device="cuda:0", seed=0,
                  max_episode_steps=None, autoreset=True, domain_randomization=None, env_offset=0,
                  iterations=None, debug=False, solver="newton", observation_width=640, observation_height=480,
                  variant="joint", reward64=False, nsubstep=None, convex="epa", episode_stats=False, channels_first=False,
-                 flat_pixels=False, depth=False, segmentation=False):
+                 flat_pixels=False, depth=False, segmentation=False, cameras=None):
         torch = _torch()
         if obs_type not in ("so100_state", "so100_pixels_agent_pos"):
             raise NotImplementedError(f"obs_type={obs_type!r}: 'so100_state' or 'so100_pixels_agent_pos'")
@@ -134,6 +140,13 @@ class SO100VecEnv:
             raise ValueError("channels_first / flat_pixels need obs_type='so100_pixels_agent_pos'")
         if (depth or segmentation) and obs_type != "so100_pixels_agent_pos":
             raise ValueError("depth / segmentation need obs_type='so100_pixels_agent_pos'")
+        if cameras is not None:
+            from .render import check_camera_names
+            if obs_type != "so100_pixels_agent_pos":
+                raise ValueError("cameras need obs_type='so100_pixels_agent_pos'")
+            cameras = check_camera_names(cameras)
+            if not all(isinstance(c, str) for c in cameras):
+                raise ValueError("cameras: a tuple of camera names")
         if domain_randomization and domain_randomization.get("visual") is not None:
             if obs_type != "so100_pixels_agent_pos":
                 raise ValueError("domain_randomization['visual'] needs obs_type='so100_pixels_agent_pos'")
@@ -202,11 +215,18 @@ class SO100VecEnv:
         self.pixels = self.final_pixels = self.renderer = self.pixels_flat = None
         self.depth = self.segmentation = self.final_depth = self.final_segmentation = None
         self.channels_first = bool(channels_first)
+        self.camera_names = None
         if obs_type == "so100_pixels_agent_pos":
-            from .render import CameraRenderer, SEG_BACKGROUND
-            self.renderer = CameraRenderer(self, observation_width, observation_height,
-                                           channels_first=self.channels_first, depth=depth,
-                                           segmentation=segmentation)
+            from .render import CameraRenderer, MultiCameraRenderer, SEG_BACKGROUND
+            if cameras is None:
+                self.renderer = CameraRenderer(self, observation_width, observation_height,
+                                               channels_first=self.channels_first, depth=depth,
+                                               segmentation=segmentation)
+            else:
+                self.renderer = MultiCameraRenderer(self, observation_width, observation_height, cameras=cameras,
+                                                    channels_first=self.channels_first, depth=depth,
+                                                    segmentation=segmentation)
+                self.camera_names = self.renderer.camera_names
             if self._visual is not None:
                 self._sample_views()
             self.pixels = self.renderer.pixels
@@ -217,7 +237,7 @@ class SO100VecEnv:
                 self.final_segmentation = None if self.segmentation is None else \
                     torch.full_like(self.segmentation, SEG_BACKGROUND)
             if flat_pixels:
-                self._npix = 3 * self.renderer.width * self.renderer.height
+                self._npix = 3 * self.renderer.width * self.renderer.height * (1 if cameras is None else len(cameras))
                 self.pixels_flat = torch.zeros(n, self._npix + 6, dtype=f32, device=d)
 
     # ------------------------------------------------------------------ plumbing

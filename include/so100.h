@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SO100_ABI_VERSION 21  /* 21: so100_render_aux / so100_aux_out / so100_render_labels / so100_aux_out_bytes (depth and segmentation images from the render launch);  20: so100_view / so100_render_views / so100_render_materials / so100_views_sample / so100_view_bytes (camera, lights and colours per env);  19: so100_render_to / so100_image_out (one render launch, several sinks: hwc, chw, flat float32);  18: env packing of the fused step (so100_set_env_packing, so100_env_packing, so100_env_order, so100_env_cost, so100_wave_cost);  17: so100_pool_stats (the fused step's contact-record pool, sized never to run out);  16: so100_source_hash;  15: the EE variant's mocap marker box collides (SO100_NGEOM 16, SO100_NPAIR 209, SO100_NCON_MAX 643, debug stride 3,922);  14: no per-env contact cap (SO100_NCON_MAX: every pair at its collider's maximum), debug stride 3,436 (SO100_DBG_OVF), ncon_dropped always 0, status -3 for a caught C++ exception;  13: so100_buffers.ep_return / ep_final / ep_accum (device-side episode statistics);  12: so100_model.convex (GJK/EPA mesh collider, MuJoCo 3.3.3 default), box-box up to 8 contacts, cube-table one convex contact;  11: so100_buffers.ncon_dropped, debug stride 160 (contact friction forces), so100_set_fused_build;  10: so100_hull_cells (MPR support lookup);  9: pad/link-hull pairs (SO100_NPAIR 191);  8: fused step kernel, so100_set_step_mode;  7: reward64 buffer;  6: Base hull + pad pairs (SO100_NPAIR 155, SO100_NHULL_ALL 10); 5: EE/mocap weld, render API */
+#define SO100_ABI_VERSION 22  /* 22: so100_cams / so100_render_cams / so100_cams_bytes (several cameras in one render launch, cameras mounted on a body);  21: so100_render_aux / so100_aux_out / so100_render_labels / so100_aux_out_bytes (depth and segmentation images from the render launch);  20: so100_view / so100_render_views / so100_render_materials / so100_views_sample / so100_view_bytes (camera, lights and colours per env);  19: so100_render_to / so100_image_out (one render launch, several sinks: hwc, chw, flat float32);  18: env packing of the fused step (so100_set_env_packing, so100_env_packing, so100_env_order, so100_env_cost, so100_wave_cost);  17: so100_pool_stats (the fused step's contact-record pool, sized never to run out);  16: so100_source_hash;  15: the EE variant's mocap marker box collides (SO100_NGEOM 16, SO100_NPAIR 209, SO100_NCON_MAX 643, debug stride 3,922);  14: no per-env contact cap (SO100_NCON_MAX: every pair at its collider's maximum), debug stride 3,436 (SO100_DBG_OVF), ncon_dropped always 0, status -3 for a caught C++ exception;  13: so100_buffers.ep_return / ep_final / ep_accum (device-side episode statistics);  12: so100_model.convex (GJK/EPA mesh collider, MuJoCo 3.3.3 default), box-box up to 8 contacts, cube-table one convex contact;  11: so100_buffers.ncon_dropped, debug stride 160 (contact friction forces), so100_set_fused_build;  10: so100_hull_cells (MPR support lookup);  9: pad/link-hull pairs (SO100_NPAIR 191);  8: fused step kernel, so100_set_step_mode;  7: reward64 buffer;  6: Base hull + pad pairs (SO100_NPAIR 155, SO100_NHULL_ALL 10); 5: EE/mocap weld, render API */
 
 /* tasks (gym_so100/__init__.py:4-32 ids; single_arm.py task classes) */
 #define SO100_TASK_CUBE_TO_BIN 0          /* gym_so100/SO100CubeToBin-v0, TimeLimit 700 */
@@ -319,6 +319,32 @@ int so100_aux_out_bytes(void);
 int so100_render_aux(so100_env* env, const float* qpos, const uint8_t* mask, const so100_camera* cam,
                      const so100_view* views, int width, int height, const so100_image_out* out,
                      const so100_aux_out* aux, void* stream);
+
+/* ---- (ABI 22) several cameras in one launch, world-fixed or mounted on a body (the reference's observation is `top`,
+ * `angle` and `front_close`, tasks/single_arm.py:88-102, and its arm carries `left_wrist` on Fixed_Jaw,
+ * so_arm100.xml:126).  The launch's grid is (env, camera): block (env, c) is so100_render_aux's block drawing env from
+ * cam[c] and views[c * N + env] into slot env * ncam + c of every sink.  DESIGN.md §3.7. */
+#define SO100_MAX_CAMS 4
+typedef struct so100_cams {
+  uint32_t size;                          /* sizeof(so100_cams): the callee rejects a mismatch */
+  int32_t  ncam;                          /* 1..SO100_MAX_CAMS */
+  so100_camera cam[SO100_MAX_CAMS];       /* track, znear and nlight are per camera */
+  int32_t  frame_body[SO100_MAX_CAMS];    /* 0: cam[c].pos / mat are in the world, used as they are; 1..8: in that body's
+                                             frame (1 Base, 2..7 arm links, 8 cube): pos_w = R_b pos + p_b per env, then
+                                             track = 1: the targetbody rule from pos_w; track = 0: R_b mat (a rigid mount).
+                                             A view record's pos and mat are in the same frame as its camera's. */
+} so100_cams;
+int so100_cams_bytes(void);
+/* Sinks (K = ncam; with K = 1 so100_render_aux's): hwc [N][K][H][W][3], chw [N][K][3][H][W], depth and label
+ * [N][K][H][W], flat [N][flat_pitch] with camera c in floats [c*3HW, (c+1)*3HW) and flat_pitch >= K*3HW.  views is
+ * camera-major, [K][N] (each camera's records a contiguous [N] array so100_views_sample fills), or NULL.  qpos and mask
+ * are per env: an env is drawn in all its cameras or in none, and nothing outside a drawn slot's span is written.
+ * Enqueued on stream, never synchronises.  Nonzero (text in so100_last_error), before any device work, for a wrong
+ * `size` in any of the three structs (checked first), NULL cams, ncam outside 1..SO100_MAX_CAMS, a frame_body outside
+ * 0..8, flat_pitch < ncam*3HW, width*height*ncam > 1 << 22, and for what so100_render_aux rejects. */
+int so100_render_cams(so100_env* env, const float* qpos, const uint8_t* mask, const so100_cams* cams,
+                      const so100_view* views, int width, int height, const so100_image_out* out,
+                      const so100_aux_out* aux, void* stream);
 
 /* Batched sparse GoalEnv reward (env.py:341-353): out[i] = ||a_i - d_i|| < threshold ? 0 : -1. */
 int so100_goal_reward(so100_env* env, int n, const float* achieved, const float* desired, float* out,
