@@ -38,6 +38,10 @@ hipError_t launch_render_aux(const DevModel*, const float4*, const int*, const u
 hipError_t launch_render_cams(const DevModel*, const float4*, const int*, const uint32_t*, const uint8_t*, const uint8_t*,
                               int, const float*, const uint8_t*, const so100_cams&, const so100_view*, int, int, int,
                               const so100_image_out&, const so100_aux_out&, hipStream_t);
+hipError_t launch_render_shadow(const DevModel*, const float4*, const int*, const uint32_t*, const uint8_t*,
+                                const uint8_t*, const uint8_t*, int, const float*, const uint8_t*, const so100_cams&,
+                                const so100_view*, int, int, int, const so100_image_out&, const so100_aux_out&,
+                                const so100_shadow&, hipStream_t);
 hipError_t launch_views_sample(const so100_view_dr&, const so100_camera&, const uint32_t*, const uint32_t*,
                                const uint8_t*, so100_view*, int, int, hipStream_t);
 hipError_t alloc_workspace(int, Workspace*);
@@ -97,6 +101,7 @@ struct so100_env {
   int r_ntri = 0;
   uint8_t* r_mat = nullptr;     // per-triangle material ids of that mesh (so100_render_materials), or none yet
   uint8_t* r_label = nullptr;   // per-triangle labels of that mesh (so100_render_labels), or none yet
+  uint8_t* r_caster = nullptr;  // per-triangle shadow-caster bytes of that mesh (so100_render_casters), or none yet
   // profiling (so100_profile_enable): events[step][prof_per] (2 nsubstep + 2 split, 2 fused)
   std::vector<hipEvent_t> prof_ev;
   int prof_cap = 0, prof_used = 0, prof_per = 0;
@@ -798,6 +803,7 @@ static int so100_destroy_impl(so100_env* env) {
   if (env->r_rgb) (void)hipFree(env->r_rgb);
   if (env->r_mat) (void)hipFree(env->r_mat);
   if (env->r_label) (void)hipFree(env->r_label);
+  if (env->r_caster) (void)hipFree(env->r_caster);
   hipError_t e = hipFree(env->d_model);
   if (env->d_cand) (void)hipFree(env->d_cand);
   hipError_t e2 = free_chunks(env);
@@ -1193,7 +1199,9 @@ static int so100_render_mesh_impl(so100_env* env, const float* tri, const int* b
   if (env->r_rgb) (void)hipFree(env->r_rgb);
   if (env->r_mat) (void)hipFree(env->r_mat);
   if (env->r_label) (void)hipFree(env->r_label);
+  if (env->r_caster) (void)hipFree(env->r_caster);
   env->r_tri = nullptr; env->r_body = nullptr; env->r_rgb = nullptr; env->r_mat = nullptr; env->r_label = nullptr;
+  env->r_caster = nullptr;
   env->r_ntri = 0;
   hipError_t e = hipMalloc(&env->r_tri, t.size() * sizeof(float4));
   if (e == hipSuccess) e = hipMalloc(&env->r_body, (size_t)ntri * sizeof(int));
@@ -1342,47 +1350,51 @@ static int so100_render_aux_impl(so100_env* env, const float* qpos, const uint8_
                        aux ? aux : &no_aux);
 }
 
-// the launch over (env, camera): so100_render_aux's checks, per camera where they are the camera's
-static int so100_render_cams_impl(so100_env* env, const float* qpos, const uint8_t* mask, const so100_cams* cams,
-                                  const so100_view* views, int width, int height, const so100_image_out* out,
-                                  const so100_aux_out* aux, void* stream) {
+// the launch over (env, camera): so100_render_aux's checks, per camera where they are the camera's.  With sh it is
+// so100_render_shadow (`who` names the call in the messages): the same checks, then the shadow struct's
+static int cams_launch(const char* who, so100_env* env, const float* qpos, const uint8_t* mask, const so100_cams* cams,
+                       const so100_view* views, int width, int height, const so100_image_out* out,
+                       const so100_aux_out* aux, const so100_shadow* sh, void* stream) {
   // the structs' sizes first: nothing else of them is read before they are known to be this library's layout
-  if (cams && cams->size != sizeof(so100_cams))
-    return size_mismatch("so100_render_cams", "so100_cams", cams->size, sizeof(so100_cams));
+  if (cams && cams->size != sizeof(so100_cams)) return size_mismatch(who, "so100_cams", cams->size, sizeof(so100_cams));
   if (out && out->size != sizeof(so100_image_out))
-    return size_mismatch("so100_render_cams", "so100_image_out", out->size, sizeof(so100_image_out));
+    return size_mismatch(who, "so100_image_out", out->size, sizeof(so100_image_out));
   if (aux && aux->size != sizeof(so100_aux_out))
-    return size_mismatch("so100_render_cams", "so100_aux_out", aux->size, sizeof(so100_aux_out));
-  if (!cams) return fail("so100_render_cams: NULL cams");
-  char msg[160];
+    return size_mismatch(who, "so100_aux_out", aux->size, sizeof(so100_aux_out));
+  if (sh && sh->size != sizeof(so100_shadow))
+    return size_mismatch(who, "so100_shadow", sh->size, sizeof(so100_shadow));
+  char msg[200];
+  auto bad = [&](const char* what) {
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    return fail(msg);
+  };
+  if (!cams) return bad("NULL cams");
   if (cams->ncam < 1 || cams->ncam > SO100_MAX_CAMS) {
-    snprintf(msg, sizeof(msg), "so100_render_cams: ncam %d, expected 1..%d", cams->ncam, SO100_MAX_CAMS);
+    snprintf(msg, sizeof(msg), "%s: ncam %d, expected 1..%d", who, cams->ncam, SO100_MAX_CAMS);
     return fail(msg);
   }
   for (int c = 0; c < cams->ncam; c++)
     if (cams->frame_body[c] < 0 || cams->frame_body[c] >= SO100_NBODY) {
-      snprintf(msg, sizeof(msg), "so100_render_cams: frame_body[%d] %d, expected 0 (world) or 1..%d", c,
-               cams->frame_body[c], SO100_NBODY - 1);
+      snprintf(msg, sizeof(msg), "%s: frame_body[%d] %d, expected 0 (world) or 1..%d", who, c, cams->frame_body[c],
+               SO100_NBODY - 1);
       return fail(msg);
     }
-  auto bad = [&](const char* what) {
-    snprintf(msg, sizeof(msg), "so100_render_cams: %s", what);
-    return fail(msg);
-  };
   // what the arguments alone decide comes before the env is looked at
   const int K = cams->ncam;
   if (width <= 0 || height <= 0 || width > 4096 || (long)width * height * K > (1L << 22))
     return bad("bad image size (width <= 4096, width*height*ncam <= 2^22)");
   if (out && out->flat && out->flat_pitch < (int64_t)3 * width * height * K) return bad("flat_pitch < ncam*3*H*W");
-  if (!(out && (out->hwc || out->chw || out->flat)) && !(aux && (aux->depth || aux->label)))
-    return bad("no sink (hwc, chw, flat, depth and label are all NULL)");
+  if (!(out && (out->hwc || out->chw || out->flat)) && !(aux && (aux->depth || aux->label)) &&
+      !(sh && sh->shadow_out))
+    return bad(sh ? "no sink (hwc, chw, flat, depth, label and shadow_out are all NULL)"
+                  : "no sink (hwc, chw, flat, depth and label are all NULL)");
   if (!env) return bad("NULL env");
   if (!qpos) return bad("bad arguments");
   if (env->r_ntri <= 0) return bad("no render mesh (so100_render_mesh)");
   for (int c = 0; c < K; c++) {
     const so100_camera& cam = cams->cam[c];
     if (cam.nlight < 0 || cam.nlight > SO100_MAX_LIGHTS || !(cam.fovy > 0.f && cam.fovy < 180.f)) {
-      snprintf(msg, sizeof(msg), "so100_render_cams: bad camera %d", c);
+      snprintf(msg, sizeof(msg), "%s: bad camera %d", who, c);
       return fail(msg);
     }
   }
@@ -1390,11 +1402,68 @@ static int so100_render_cams_impl(so100_env* env, const float* qpos, const uint8
   if (aux && aux->label && !env->r_label) return bad("no labels (so100_render_labels)");
   const so100_image_out none{(uint32_t)sizeof(so100_image_out), nullptr, nullptr, nullptr, 0};
   const so100_aux_out no_aux{(uint32_t)sizeof(so100_aux_out), nullptr, nullptr};
+  if (sh) {
+    for (int c = 0; c < K; c++)
+      if (sh->light < -1 || sh->light >= cams->cam[c].nlight) {
+        snprintf(msg, sizeof(msg), "%s: light %d, expected -1 (none) or 0..%d (camera %d's lights)", who, sh->light,
+                 cams->cam[c].nlight - 1, c);
+        return fail(msg);
+      }
+    if (sh->map_size < 8 || sh->map_size > SO100_SHADOW_MAP_MAX || sh->map_size % 8 != 0) {
+      snprintf(msg, sizeof(msg), "%s: map_size %d, expected a multiple of 8 in 8..%d (the map lives in LDS)", who,
+               sh->map_size, SO100_SHADOW_MAP_MAX);
+      return fail(msg);
+    }
+    if (!(std::isfinite(sh->radius) && sh->radius > 0.f)) return bad("radius must be finite and > 0");
+    if (!(std::isfinite(sh->bias) && sh->bias >= 0.f)) return bad("bias must be finite and >= 0");
+    if (!(std::isfinite(sh->center[0]) && std::isfinite(sh->center[1]) && std::isfinite(sh->center[2])))
+      return bad("center must be finite");
+    if (!env->r_caster) return bad("no casters (so100_render_casters)");
+    DeviceGuard g(env->device);
+    hipError_t e = so100::launch_render_shadow(env->d_model, env->r_tri, env->r_body, env->r_rgb, env->r_mat,
+                                               env->r_label, env->r_caster, env->r_ntri, qpos, mask, *cams, views,
+                                               env->n, width, height, out ? *out : none, aux ? *aux : no_aux, *sh,
+                                               (hipStream_t)stream);
+    return e == hipSuccess ? 0 : fail_hip(who, e);
+  }
   DeviceGuard g(env->device);
   hipError_t e = so100::launch_render_cams(env->d_model, env->r_tri, env->r_body, env->r_rgb, env->r_mat, env->r_label,
                                            env->r_ntri, qpos, mask, *cams, views, env->n, width, height,
                                            out ? *out : none, aux ? *aux : no_aux, (hipStream_t)stream);
-  return e == hipSuccess ? 0 : fail_hip("so100_render_cams", e);
+  return e == hipSuccess ? 0 : fail_hip(who, e);
+}
+
+static int so100_render_cams_impl(so100_env* env, const float* qpos, const uint8_t* mask, const so100_cams* cams,
+                                  const so100_view* views, int width, int height, const so100_image_out* out,
+                                  const so100_aux_out* aux, void* stream) {
+  return cams_launch("so100_render_cams", env, qpos, mask, cams, views, width, height, out, aux, nullptr, stream);
+}
+
+static int so100_render_casters_impl(so100_env* env, const uint8_t* caster, int ntri) {
+  if (!env || !caster) return fail("so100_render_casters: bad arguments");
+  if (env->r_ntri <= 0) return fail("so100_render_casters: no render mesh (so100_render_mesh)");
+  if (ntri != env->r_ntri) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "so100_render_casters: ntri %d, the mesh has %d", ntri, env->r_ntri);
+    return fail(msg);
+  }
+  DeviceGuard g(env->device);
+  hipError_t e = hipSuccess;
+  if (!env->r_caster) e = hipMalloc(&env->r_caster, (size_t)ntri);
+  if (e == hipSuccess) e = hipMemcpy(env->r_caster, caster, (size_t)ntri, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (env->r_caster) (void)hipFree(env->r_caster);
+    env->r_caster = nullptr;
+    return fail_hip("so100_render_casters", e);
+  }
+  return 0;
+}
+
+static int so100_render_shadow_impl(so100_env* env, const float* qpos, const uint8_t* mask, const so100_cams* cams,
+                                    const so100_view* views, int width, int height, const so100_image_out* out,
+                                    const so100_aux_out* aux, const so100_shadow* shadow, void* stream) {
+  if (!shadow) return fail("so100_render_shadow: NULL shadow");
+  return cams_launch("so100_render_shadow", env, qpos, mask, cams, views, width, height, out, aux, shadow, stream);
 }
 
 static int so100_views_sample_impl(so100_env* env, const so100_view_dr* dr, const so100_camera* cam,
@@ -1468,6 +1537,26 @@ int so100_render_cams(so100_env* env, const float* qpos, const uint8_t* mask, co
     return so100_render_cams_impl(env, qpos, mask, cams, views, width, height, out, aux, stream);
   } catch (...) {
     return caught("so100_render_cams");
+  }
+}
+
+int so100_shadow_bytes(void) { return (int)sizeof(so100_shadow); }
+
+int so100_render_casters(so100_env* env, const uint8_t* caster, int ntri) {
+  try {
+    return so100_render_casters_impl(env, caster, ntri);
+  } catch (...) {
+    return caught("so100_render_casters");
+  }
+}
+
+int so100_render_shadow(so100_env* env, const float* qpos, const uint8_t* mask, const so100_cams* cams,
+                        const so100_view* views, int width, int height, const so100_image_out* out,
+                        const so100_aux_out* aux, const so100_shadow* shadow, void* stream) {
+  try {
+    return so100_render_shadow_impl(env, qpos, mask, cams, views, width, height, out, aux, shadow, stream);
+  } catch (...) {
+    return caught("so100_render_shadow");
   }
 }
 

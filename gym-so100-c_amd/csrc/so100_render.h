@@ -1,8 +1,9 @@
-// so100_render.h - the render kernel's body, shared by its five launches: so100_render.hip (the hwc image alone),
+// so100_render.h - the render kernel's body, shared by its six launches: so100_render.hip (the hwc image alone),
 // so100_render_sinks.hip (so100_render_to's further sinks), so100_render_views.hip (so100_render_views: camera,
 // lights and colours per env), so100_render_aux.hip (so100_render_aux: the depth and label sinks, with or without
-// views) and so100_render_cams.hip (so100_render_cams: the aux launch over a grid of (env, camera), with cameras that
-// ride on a body).  One translation unit per kernel: with two instantiations in one unit the hwc-only kernel was scheduled
+// views), so100_render_cams.hip (so100_render_cams: the aux launch over a grid of (env, camera), with cameras that
+// ride on a body) and so100_render_shadow.hip (so100_render_shadow: the cams launch with one light occluded per pixel
+// by a shadow map the block builds in LDS).  One translation unit per kernel: with two instantiations in one unit the hwc-only kernel was scheduled
 // differently and measured slower.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -62,6 +63,31 @@ struct RenderCamsArgs : RenderAuxArgs {
   so100_camera cams[SO100_MAX_CAMS];
   int frame_body[SO100_MAX_CAMS];       // 0 world, 1..8 the body the camera is mounted on
 };
+// the launch with cast shadows (so100_render_shadow): the cams launch whose blocks first rasterise the caster triangles
+// into an orthographic depth map along light `light`, kept in LDS through all bands, and carry beside the key a second
+// one whose colour is shaded with that light's diffuse taken as 0: a pixel the map occludes takes the second key's
+// colour (DESIGN.md 3.7 "Shadows")
+struct RenderShadowArgs : RenderCamsArgs {
+  const uint8_t* caster;                // [ntri] non-zero: the triangle is drawn into the shadow map
+  int light;                            // the casting light, < nlight of every camera; -1: nothing casts
+  int map_size;                         // S: the map is S x S texels, S <= kShadowMapMax
+  float center[3];                      // the map covers the disc of `radius` about `center` across the light
+  float radius;
+  float bias;                           // metres: occluded iff map depth < the point's depth - bias
+  uint8_t* shadow;                      // [n][ncam][height][width] or null: 1 occluded, 0 lit, background 0
+};
+constexpr int kShadowMapMax = SO100_SHADOW_MAP_MAX;        // 16 KB of LDS
+constexpr uint32_t kShadowEmpty = 0xFFFFFFFFu;
+// float32 -> uint32 that orders as the floats do (for atomicMin), and back
+DEV uint32_t shadow_encode(float d) {
+  const uint32_t u = __float_as_uint(d);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+DEV float shadow_decode(uint32_t e) { return __uint_as_float((e & 0x80000000u) ? (e & 0x7FFFFFFFu) : ~e); }
+// the light's frame and the map's placement, in LDS
+struct ShadowFrame {
+  float d[3], u[3], v[3];               // the light's direction and the map's two axes
+};
 constexpr int kViewWords = (int)(sizeof(so100_view) / sizeof(uint32_t));
 static_assert(sizeof(so100_view) == 160 && kViewWords == 40, "so100_view: 40 dwords");
 // the env's record in LDS, filled one dword per thread
@@ -112,14 +138,15 @@ DEV uint32_t shade(const Cam& c, int nlight, const float* cm, const float* p0, c
 template <class Args>
 DEV decltype(auto) view_source(const Args& a, const ViewLds& vl) {
   if constexpr (std::is_same<Args, RenderViewArgs>::value || std::is_same<Args, RenderAuxArgs>::value ||
-                std::is_same<Args, RenderCamsArgs>::value)
+                std::is_same<Args, RenderCamsArgs>::value || std::is_same<Args, RenderShadowArgs>::value)
     return (vl.v);
   else return (a.cam);
 }
-// the launch's camera: the block's own of RenderCamsArgs, a.cam in the other four
+// the launch's camera: the block's own of RenderCamsArgs / RenderShadowArgs, a.cam in the other four
 template <class Args>
 DEV const so100_camera& launch_cam(const Args& a) {
-  if constexpr (std::is_same<Args, RenderCamsArgs>::value) return a.cams[blockIdx.y];
+  if constexpr (std::is_same<Args, RenderCamsArgs>::value || std::is_same<Args, RenderShadowArgs>::value)
+    return a.cams[blockIdx.y];
   else return a.cam;
 }
 
@@ -127,18 +154,27 @@ DEV const so100_camera& launch_cam(const Args& a) {
 // Args = RenderSinkArgs: every non-null sink of a.out / a.chw / a.flat is written from the same band;
 // Args = RenderViewArgs: the same sinks, drawn from views[env] (not referenced, vl costs the other two no LDS);
 // Args = RenderAuxArgs: those sinks and a.depth / a.seg, from views[env] or (a.views null) from a.cam through vl;
-// Args = RenderCamsArgs: the aux kernel's block per (env, camera): grid (n, ncam), see the struct.
+// Args = RenderCamsArgs: the aux kernel's block per (env, camera): grid (n, ncam), see the struct;
+// Args = RenderShadowArgs: the cams kernel with the shadow map, the second key and the shadow sink, see the struct.
 template <class Args>
 __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
   constexpr bool kSinks = sizeof(Args) != sizeof(RenderArgs);
   constexpr bool kView = std::is_same<Args, RenderViewArgs>::value;
-  constexpr bool kCams = std::is_same<Args, RenderCamsArgs>::value;
+  constexpr bool kShadow = std::is_same<Args, RenderShadowArgs>::value;
+  constexpr bool kCams = std::is_same<Args, RenderCamsArgs>::value || kShadow;
   constexpr bool kAux = std::is_same<Args, RenderAuxArgs>::value || kCams;
   constexpr int kColShift = kAux ? 8 : 0;                  // the colour's place in the key's lower half
   __shared__ ViewLds vl;
   __shared__ EnvShared sh;
   __shared__ float frm[SO100_NBODY][12];           // body rotation (9) + position (3)
   __shared__ unsigned long long zb[kTilePx];
+  // the shadow kernel alone (not referenced, these cost the other five no LDS): the key with the dark colour, after the
+  // shadow test the pixel's 0 / 1; the record with the casting light's diffuse 0; the map and its frame.  The bands are
+  // the other kernels' bands: a triangle's depth is then computed by the same phase (A or B) as in so100_render_cams
+  __shared__ unsigned long long zd[kShadow ? kTilePx : 1];
+  __shared__ ViewLds vd;
+  __shared__ uint32_t smap[kShadow ? kShadowMapMax * kShadowMapMax : 1];
+  __shared__ ShadowFrame sf;
   __shared__ int big[kBigCap];
   __shared__ int nbig;
   __shared__ float cmat[9];                        // camera frame (columns x, y, z) for this env
@@ -229,8 +265,72 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
     } else {
       for (int k = 0; k < 9; k++) cmat[k] = cv.mat[k];
     }
+    if constexpr (kShadow) {
+      // the dark record: this block's record (a mounted camera's pos already the world's) without the casting light
+      for (int k = 0; k < kViewWords; k++) vd.w[k] = vl.w[k];
+      if (a.light >= 0) {
+        vd.v.light_diffuse[a.light] = 0.f;
+        // the light's frame: d the direction, u = normalize(z x d) (x if d is vertical), v = d x u
+        const float* ld = vl.v.light_dir[a.light];
+        const float n = sqrtf(dot3(ld, ld));
+        for (int k = 0; k < 3; k++) sf.d[k] = ld[k] / n;
+        float u[3] = {-sf.d[1], sf.d[0], 0.f};             // z x d
+        const float un = sqrtf(dot3(u, u));
+        if (un < 1e-6f) { u[0] = 1.f; u[1] = u[2] = 0.f; } else { u[0] /= un; u[1] /= un; u[2] /= un; }
+        for (int k = 0; k < 3; k++) sf.u[k] = u[k];
+        cross3(sf.v, sf.d, u);
+      }
+    }
+  }
+  if constexpr (kShadow) {
+    for (int i = tid; i < a.map_size * a.map_size; i += kRenderThreads) smap[i] = kShadowEmpty;
   }
   __syncthreads();
+  if constexpr (kShadow) {
+    // ---- the shadow map: every caster triangle, one per thread, with the camera rasteriser's rules on the map's S x S
+    // texels (centres at +0.5, inclusive edges, the area reject); depth along d, linear in the edge weights
+    // (no FMA contraction in the map's and the test's arithmetic: a product rounded differently moves a texel's or a
+    // pixel's verdict, and the float32 restatement the mask is held to rounds every product)
+    if (a.light >= 0) {
+#pragma clang fp contract(off)
+      auto dotp = [](const float* p, const float* q) { return p[0] * q[0] + p[1] * q[1] + p[2] * q[2]; };
+      const int S = a.map_size;
+      const float sc = 0.5f / a.radius;
+      for (int t = tid; t < a.ntri; t += kRenderThreads) {
+        if (!a.caster[t]) continue;
+        const float* R = frm[a.tri_body[t]];
+        float sx[3], sy[3], dz[3];
+#pragma unroll
+        for (int v = 0; v < 3; v++) {
+          const float4 q = a.tri[3 * t + v];
+          const float w[3] = {R[0] * q.x + R[1] * q.y + R[2] * q.z + R[9] - a.center[0],
+                              R[3] * q.x + R[4] * q.y + R[5] * q.z + R[10] - a.center[1],
+                              R[6] * q.x + R[7] * q.y + R[8] * q.z + R[11] - a.center[2]};
+          sx[v] = (dotp(w, sf.u) * sc + 0.5f) * (float)S;
+          sy[v] = (dotp(w, sf.v) * sc + 0.5f) * (float)S;
+          dz[v] = dotp(w, sf.d);
+        }
+        const float area = (sx[1] - sx[0]) * (sy[2] - sy[0]) - (sx[2] - sx[0]) * (sy[1] - sy[0]);
+        if (!(fabsf(area) > 1e-12f)) continue;
+        const int bx0 = max(0, (int)floorf(fminf(sx[0], fminf(sx[1], sx[2])) - 0.5f));
+        const int bx1 = min(S - 1, (int)ceilf(fmaxf(sx[0], fmaxf(sx[1], sx[2])) - 0.5f));
+        const int by0 = max(0, (int)floorf(fminf(sy[0], fminf(sy[1], sy[2])) - 0.5f));
+        const int by1 = min(S - 1, (int)ceilf(fmaxf(sy[0], fmaxf(sy[1], sy[2])) - 0.5f));
+        const float sg = area > 0.f ? 1.f : -1.f, inv = 1.f / area;
+        for (int y = by0; y <= by1; y++)
+          for (int x = bx0; x <= bx1; x++) {
+            const float px = (float)x + 0.5f, py = (float)y + 0.5f;
+            const float w0 = (sx[2] - sx[1]) * (py - sy[1]) - (sy[2] - sy[1]) * (px - sx[1]);
+            const float w1 = (sx[0] - sx[2]) * (py - sy[2]) - (sy[0] - sy[2]) * (px - sx[2]);
+            const float w2 = (sx[1] - sx[0]) * (py - sy[0]) - (sy[1] - sy[0]) * (px - sx[0]);
+            if (w0 * sg < 0.f || w1 * sg < 0.f || w2 * sg < 0.f) continue;
+            const float dep = (w0 * dz[0] + w1 * dz[1] + w2 * dz[2]) * inv;
+            if (dep == dep) atomicMin(&smap[y * S + x], shadow_encode(dep));      // bx, by are inside the map
+          }
+      }
+    }
+    __syncthreads();
+  }
 
   const float th = tanf(0.5f * cv.fovy * 0.017453292519943295f);
   const float aspect = (float)W / (float)H;
@@ -241,9 +341,15 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
     const int y1 = min(H, y0 + band);
     const int npx = (y1 - y0) * W;
     for (int i = tid; i < npx; i += kRenderThreads) zb[i] = ~0ull;
+    if constexpr (kShadow) {
+      for (int i = tid; i < npx; i += kRenderThreads) zd[i] = ~0ull;
+    }
     if (tid == 0) nbig = 0;
     __syncthreads();
 
+    // the shadow kernel alone: the lower half of the second key of the triangle this thread has set up, its colour
+    // without the casting light (setup leaves it here for raster)
+    uint32_t cold = 0;
     // screen-space triangle: pixel x to the right, y down; depth along the camera's -z
     auto setup = [&](int t, float* sx, float* sy, float* iz, uint32_t& col, int& bx0, int& bx1, int& by0,
                      int& by1) -> bool {
@@ -285,6 +391,8 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
       else base = a.tri_rgb[t];
       col = shade(cv, lc.nlight, cmat, pw[0], pw[1], pw[2], base);
       if constexpr (kAux) col = (col << 8) | (a.label ? (uint32_t)a.label[t] : 0u);   // the key's lower half
+      if constexpr (kShadow)
+        cold = (shade(vd.v, lc.nlight, cmat, pw[0], pw[1], pw[2], base) << 8) | (col & 0xFFu);
       return true;
     };
     // one pixel of a set-up triangle: edge functions at the pixel centre, perspective-correct depth
@@ -302,6 +410,8 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
       const float depth = 1.f / izp;
       const unsigned long long key = ((unsigned long long)__float_as_uint(depth) << 32) | col;
       atomicMin(&zb[(y - y0) * W + x], key);
+      if constexpr (kShadow)
+        atomicMin(&zd[(y - y0) * W + x], ((unsigned long long)__float_as_uint(depth) << 32) | cold);
     };
 
     // ---- phase A: one triangle per thread; large ones are listed for phase B
@@ -329,6 +439,38 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
       for (int i = tid; i < cnt; i += kRenderThreads) raster(sx, sy, iz, col, bx0 + i % bw, by0 + i / bw);
     }
     __syncthreads();
+    if constexpr (kShadow) {
+#pragma clang fp contract(off)
+      auto dotp = [](const float* p, const float* q) { return p[0] * q[0] + p[1] * q[1] + p[2] * q[2]; };
+      // ---- the shadow test, once per pixel with a winning key: the point the pixel's centre sees at the key's depth,
+      // looked up in the map without filtering.  An occluded pixel takes the dark key's colour (depth and label stay
+      // the key's own); zd then holds the pixel's 0 / 1 for the shadow sink
+      const int S = a.map_size;
+      const float sc = 0.5f / a.radius;
+      for (int i = tid; i < npx; i += kRenderThreads) {
+        const unsigned long long key = zb[i];
+        bool dark = false;
+        if (a.light >= 0 && key != ~0ull) {
+          const int y = y0 + i / W, x = i - (i / W) * W;
+          const float depth = __uint_as_float((uint32_t)(key >> 32));
+          const float xn = (((float)x + 0.5f) / (float)W - 0.5f) * 2.f * th * aspect;
+          const float yn = (0.5f - ((float)y + 0.5f) / (float)H) * 2.f * th;
+          float p[3];
+#pragma unroll
+          for (int k = 0; k < 3; k++)
+            p[k] = cv.pos[k] + depth * (cmat[3 * k] * xn + cmat[3 * k + 1] * yn - cmat[3 * k + 2]) - a.center[k];
+          const float fa = floorf((dotp(p, sf.u) * sc + 0.5f) * (float)S);
+          const float fb = floorf((dotp(p, sf.v) * sc + 0.5f) * (float)S);
+          if (fa >= 0.f && fa < (float)S && fb >= 0.f && fb < (float)S) {       // false for NaN
+            const uint32_t e = smap[(int)fb * S + (int)fa];
+            dark = e != kShadowEmpty && shadow_decode(e) < dotp(p, sf.d) - a.bias;
+          }
+        }
+        if (dark) zb[i] = (key & ~0xFFFFFF00ull) | (zd[i] & 0xFFFFFF00ull);
+        zd[i] = dark ? 1ull : 0ull;
+      }
+      __syncthreads();
+    }
     // ---- band -> image (background: black)
     if constexpr (!kSinks) {
       for (int i = tid; i < npx; i += kRenderThreads) {
@@ -406,6 +548,23 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
           }
           if (tid < head) p[tid] = (uint8_t)lab(tid);         // head < 4
           if (tid < npx - tail) p[tail + tid] = (uint8_t)lab(tail + tid);   // npx - tail < 4
+        }
+      }
+      if constexpr (kShadow) {
+        if (a.shadow) {
+          // the pixel's 0 / 1 left in zd, with the seg plane's head / dword / tail scheme on the band's span
+          uint8_t* p = a.shadow + (slot() * H + y0) * W;
+          const int head = min(npx, (int)((4u - (uint32_t)((uintptr_t)p & 3u)) & 3u));
+          const int nquad = (npx - head) >> 2;
+          const int tail = head + 4 * nquad;
+          uint32_t* q = (uint32_t*)(p + head);                // 4-byte aligned (unused when nquad == 0)
+          auto bit = [&](int i) -> uint32_t { return (uint32_t)zd[i]; };
+          for (int k = tid; k < nquad; k += kRenderThreads) {
+            const int i = head + 4 * k;
+            q[k] = bit(i) | (bit(i + 1) << 8) | (bit(i + 2) << 16) | (bit(i + 3) << 24);
+          }
+          if (tid < head) p[tid] = (uint8_t)bit(tid);         // head < 4
+          if (tid < npx - tail) p[tail + tid] = (uint8_t)bit(tail + tid);   // npx - tail < 4
         }
       }
     }

@@ -76,6 +76,26 @@ class SO100Cams(ctypes.Structure):
             self.frame_body[c] = int(b)
 
 
+SO100_SHADOW_MAP_MAX = 64          # include/so100.h: the shadow map's largest side (it lives in LDS)
+
+
+class SO100Shadow(ctypes.Structure):
+    """Mirror of ``so100_shadow`` (include/so100.h): the casting light, the shadow map's size and placement, the depth
+    bias and the optional mask sink of one ``so100_render_shadow`` launch.  ``size`` is set to the mirror's size, which
+    the callee checks against its own."""
+    _fields_ = [("size", ctypes.c_uint32), ("light", ctypes.c_int32), ("map_size", ctypes.c_int32),
+                ("center", ctypes.c_float * 3), ("radius", ctypes.c_float), ("bias", ctypes.c_float),
+                ("shadow_out", _P)]
+
+    def __init__(self, light=-1, map_size=64, center=(0.0, 0.0, 0.0), radius=1.0, bias=0.0, shadow_out=None):
+        super().__init__()
+        self.size = ctypes.sizeof(SO100Shadow)
+        self.light, self.map_size = int(light), int(map_size)
+        self.center[:] = [float(x) for x in center]
+        self.radius, self.bias = float(radius), float(bias)
+        self.shadow_out = shadow_out
+
+
 SO100_NMATERIAL = 5
 
 
@@ -117,7 +137,7 @@ class NativeLibraryError(RuntimeError):
 _lib = None
 
 
-ABI_VERSION = 22         # include/so100.h SO100_ABI_VERSION
+ABI_VERSION = 23         # include/so100.h SO100_ABI_VERSION
 HULL_CELLG = 8           # SO100_HULL_CELLG
 HULL_NCELL = 6 * HULL_CELLG * HULL_CELLG
 
@@ -170,6 +190,11 @@ def load():
     lib.so100_cams_bytes.argtypes = []
     lib.so100_render_cams.argtypes = [_P, _P, _P, ctypes.POINTER(SO100Cams), _P, ctypes.c_int, ctypes.c_int,
                                       ctypes.POINTER(SO100ImageOut), ctypes.POINTER(SO100AuxOut), _P]
+    lib.so100_shadow_bytes.argtypes = []
+    lib.so100_render_casters.argtypes = [_P, _P, ctypes.c_int]
+    lib.so100_render_shadow.argtypes = [_P, _P, _P, ctypes.POINTER(SO100Cams), _P, ctypes.c_int, ctypes.c_int,
+                                        ctypes.POINTER(SO100ImageOut), ctypes.POINTER(SO100AuxOut),
+                                        ctypes.POINTER(SO100Shadow), _P]
     lib.so100_hull_cells.argtypes = [_P, _P, _P, ctypes.c_int]
     lib.so100_set_fused_build.argtypes = [_P, ctypes.c_int]
     lib.so100_fused_build.argtypes = [_P, ctypes.c_int]
@@ -185,7 +210,8 @@ def load():
                "so100_set_fused_build", "so100_fused_build", "so100_set_env_packing", "so100_env_packing",
                "so100_env_order", "so100_env_cost", "so100_wave_cost", "so100_view_bytes", "so100_render_materials",
                "so100_render_views", "so100_views_sample", "so100_aux_out_bytes", "so100_render_labels",
-               "so100_render_aux", "so100_cams_bytes", "so100_render_cams"):
+               "so100_render_aux", "so100_cams_bytes", "so100_render_cams", "so100_shadow_bytes",
+               "so100_render_casters", "so100_render_shadow"):
         getattr(lib, fn).restype = ctypes.c_int
     lib.so100_struct_sizes.argtypes = [_P, _P]
     lib.so100_struct_sizes.restype = ctypes.c_int
@@ -206,6 +232,9 @@ def load():
     if lib.so100_cams_bytes() != ctypes.sizeof(SO100Cams):
         raise NativeLibraryError(f"struct layout mismatch: so100_cams {lib.so100_cams_bytes()} vs "
                                  f"{ctypes.sizeof(SO100Cams)}")
+    if lib.so100_shadow_bytes() != ctypes.sizeof(SO100Shadow):
+        raise NativeLibraryError(f"struct layout mismatch: so100_shadow {lib.so100_shadow_bytes()} vs "
+                                 f"{ctypes.sizeof(SO100Shadow)}")
     _lib = lib
     return lib
 
@@ -219,7 +248,8 @@ EXPORTED_SYMBOLS = ("so100_abi_version", "so100_last_error", "so100_source_hash"
                     "so100_fused_build", "so100_set_env_packing", "so100_env_packing", "so100_env_order",
                     "so100_env_cost", "so100_wave_cost", "so100_view_bytes", "so100_render_materials",
                     "so100_render_views", "so100_views_sample", "so100_aux_out_bytes", "so100_render_labels",
-                    "so100_render_aux", "so100_cams_bytes", "so100_render_cams")
+                    "so100_render_aux", "so100_cams_bytes", "so100_render_cams", "so100_shadow_bytes",
+                    "so100_render_casters", "so100_render_shadow")
 
 
 def source_hash():

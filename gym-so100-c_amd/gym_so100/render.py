@@ -23,15 +23,22 @@ Several cameras: ``MultiCameraRenderer`` draws K <= 4 cameras of every env in on
 and cameras that ride on a body, such as the arm's own ``left_wrist`` on Fixed_Jaw (so_arm100.xml:126).  ``pixels`` is
 [N, K, H, W, 3] (or [N, K, 3, H, W]), depth and segmentation [N, K, H, W], view records [K, N, 40].
 
+Shadows: ``shadows=True`` on either renderer occludes the scene's shadow-casting light (SHADOW_LIGHT, the middle light of
+scene_so100.xml:13-16) per pixel by a shadow map that every block builds in LDS inside the one render launch (C-ABI
+``so100_render_shadow``): the arm, the jaw and the cube drop hard shadows on the table, the cue a top-down image has for
+height.  ``shadow_mask=True`` also keeps ``shadow`` (uint8, 1 = occluded).
+
 It is a rasteriser of its own, not MuJoCo's OpenGL pipeline: geometry and colours are the scene's, the
-pixel values are not MuJoCo's (no specular, shadows, fog or anti-aliasing).
+pixel values are not MuJoCo's (no specular, shadow filtering, fog or anti-aliasing).
 """
 import ctypes
+import json
 import os
 
 import numpy as np
 
 from . import _native
+from .constants import SO100_BOX_SPAWN_RANGES
 
 ASSET = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets", "so100_render.npz")
 CAMERAS = ("top", "angle", "left_pillar", "right_pillar", "front_close")
@@ -47,6 +54,10 @@ MATERIALS = ("table", "bin", "arm_light", "arm_dark", "cube")      # SO100_NMATE
 # segmentation classes (segment_labels): label k is SEG_CLASSES[k], a pixel no triangle covers is SEG_BACKGROUND
 SEG_CLASSES = ("table", "bin", "Base", "link1", "link2", "link3", "link4", "link5", "link6", "cube")
 SEG_BACKGROUND = 255
+# the light that casts shadows: scene_so100.xml:13-16 has three directional lights; the first and the third are
+# castshadow="false", the middle one (line 15, dir='-1 1 -1') keeps MuJoCo's default and casts
+SHADOW_LIGHT = 1
+MODEL_ASSET = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets", "so100_model.json")
 # the keys of a visual-randomisation dict (SO100VecEnv.set_domain_randomization(visual=...), sample_views(ranges))
 VISUAL_KEYS = ("camera_pos", "camera_rot_deg", "fovy", "ambient", "headlight", "lights", "light_rot_deg", "colors",
                "per_episode", "seed")
@@ -194,6 +205,81 @@ def segment_labels(scene):
     return lab, SEG_CLASSES
 
 
+def shadow_casters(scene):
+    """uint8 [ntri]: 1 for every triangle that is drawn into the shadow map, the default of ``so100_render_casters``:
+    all but the table's 12.  The table only receives: nothing lies under it, and leaving it out removes its
+    self-shadowing without a slope bias."""
+    mat, _ = material_ids(scene)
+    return np.ascontiguousarray(mat != MATERIALS.index("table"), dtype=np.uint8)
+
+
+def shadow_bounds(scene, model_path=MODEL_ASSET):
+    """(center [3], radius): the sphere the default shadow map covers, from the scene's vertices and the model's link
+    offsets.  It is the centre and half-diagonal of the box around (a) the bin's vertices, (b) the cube's spawn range
+    (constants.SO100_BOX_SPAWN_RANGES) grown by the cube's farthest vertex and (c) the arm's reach, the half-ball above
+    z = 0 about the Base's origin whose radius is the chain of link offsets up to Fixed_Jaw plus the farthest vertex of
+    the two jaws; the box is clipped to the table's x / y extent, beyond which nothing receives a shadow."""
+    with open(model_path) as f:
+        body_pos = np.asarray(json.load(f)["body_pos"], dtype=np.float64)
+    tri = np.asarray(scene["tri"], dtype=np.float64)
+    body = np.asarray(scene["body"])
+    mat, _ = material_ids(scene)
+
+    def far(b):
+        return float(np.linalg.norm(tri[body == b].reshape(-1, 3), axis=1).max())
+    reach = float(np.linalg.norm(body_pos[2:7], axis=1).sum()) + max(far(6), float(np.linalg.norm(body_pos[7])) + far(7))
+    lo, hi = body_pos[1] - reach, body_pos[1] + reach
+    lo[2] = 0.0
+    spawn = np.asarray(SO100_BOX_SPAWN_RANGES, dtype=np.float64)
+    binv = tri[mat == MATERIALS.index("bin")].reshape(-1, 3)
+    lo = np.minimum(lo, np.minimum(binv.min(axis=0), spawn[:, 0] - far(8)))
+    hi = np.maximum(hi, np.maximum(binv.max(axis=0), spawn[:, 1] + far(8)))
+    table = tri[mat == MATERIALS.index("table")].reshape(-1, 3)
+    lo[:2] = np.maximum(lo[:2], table.min(axis=0)[:2])
+    hi[:2] = np.minimum(hi[:2], table.max(axis=0)[:2])
+    return 0.5 * (lo + hi), float(0.5 * np.linalg.norm(hi - lo))
+
+
+SHADOW_KEYS = ("map_size", "bias", "radius", "center", "light")
+
+
+def make_shadow(scene, map_size=64, bias=0.01, radius=None, center=None, light=SHADOW_LIGHT):
+    """so100_shadow for ``so100_render_shadow``: light ``light`` (default SHADOW_LIGHT; -1: nothing casts) casts through
+    a map of map_size x map_size texels (a multiple of 8 in 8..64: it lives in LDS) over the sphere (center, radius)
+    (default shadow_bounds) with a depth bias in metres.  ValueError for what the library would refuse."""
+    c0, r0 = shadow_bounds(scene)
+    center = c0 if center is None else np.asarray(center, dtype=np.float64).reshape(-1)
+    radius = r0 if radius is None else float(radius)
+    map_size, light, bias = int(map_size), int(light), float(bias)
+    if map_size < 8 or map_size > _native.SO100_SHADOW_MAP_MAX or map_size % 8:
+        raise ValueError(f"map_size {map_size}: a multiple of 8 in 8..{_native.SO100_SHADOW_MAP_MAX} (the shadow map "
+                         f"lives in LDS)")
+    if not -1 <= light < len(scene["light_diffuse"]):
+        raise ValueError(f"light {light}: -1 (nothing casts) or 0..{len(scene['light_diffuse']) - 1}")
+    if not (np.isfinite(radius) and radius > 0.0):
+        raise ValueError(f"radius {radius!r}: finite and > 0")
+    if not (np.isfinite(bias) and bias >= 0.0):
+        raise ValueError(f"bias {bias!r}: finite and >= 0")
+    if center.shape != (3,) or not np.all(np.isfinite(center)):
+        raise ValueError("center: three finite numbers")
+    return _native.SO100Shadow(light=light, map_size=map_size, center=center, radius=radius, bias=bias)
+
+
+def shadow_options(scene, shadows):
+    """The ``shadows=`` argument of the renderers and envs (no device use): False / None -> None; True -> make_shadow's
+    defaults; a dict with keys of SHADOW_KEYS -> make_shadow(**dict).  ValueError for anything else and unknown keys."""
+    if shadows is None or shadows is False:
+        return None
+    if shadows is True:
+        shadows = {}
+    if not isinstance(shadows, dict):
+        raise ValueError(f"shadows: True, False or a dict with keys of {SHADOW_KEYS}")
+    unknown = set(shadows) - set(SHADOW_KEYS)
+    if unknown:
+        raise ValueError(f"shadows: unknown keys {sorted(unknown)}; known: {SHADOW_KEYS}")
+    return make_shadow(scene, **shadows)
+
+
 def pack_rgb8(rgb):
     """float32 [..., 3] in [0, 1] -> packed RGB8 as so100_render_mesh packs tri_rgb (float32 x * 255 + 0.5, truncated)"""
     x = np.clip(np.asarray(rgb, dtype=np.float32), np.float32(0), np.float32(1))
@@ -246,6 +332,14 @@ def view_ranges(ranges, seed):
     return dr
 
 
+def _upload_casters(venv, scene, shadows):
+    """The caster bytes belong to the mesh (a new mesh drops them): uploaded with it by a renderer with shadows, read
+    only by so100_render_shadow"""
+    if shadows is not None:
+        cast = shadow_casters(scene)
+        _native.check(venv.lib.so100_render_casters(venv._handle, cast.ctypes.data, len(cast)), "so100_render_casters")
+
+
 class CameraRenderer:
     """Renders every env of ``venv`` (an SO100VecEnv) from one camera into a persistent uint8 tensor.
 
@@ -255,16 +349,25 @@ class CameraRenderer:
 
     depth / segmentation: also keep ``depth`` (float32 [N,H,W], metres along the viewing axis, background 0) and / or
     ``segmentation`` (uint8 [N,H,W], segment_labels' classes, background SEG_BACKGROUND), filled by the launch that
-    draws ``pixels`` (C-ABI ``so100_render_aux``).  They have no channel axis: channels_first does not touch them."""
+    draws ``pixels`` (C-ABI ``so100_render_aux``).  They have no channel axis: channels_first does not touch them.
+
+    shadows: True (make_shadow's defaults) or a dict with keys of SHADOW_KEYS: the scene's shadow-casting light
+    (SHADOW_LIGHT) is occluded per pixel by a shadow map each block builds in the render launch (C-ABI
+    ``so100_render_shadow`` with K = 1; the [N,H,W,...] tensors are the same memory as [N,1,H,W,...]).  With the default
+    False every call is the one of a renderer without the option.  shadow_mask: also keep ``shadow`` (uint8 [N,H,W]:
+    1 where the light is occluded, 0 where lit and on the background); needs shadows."""
 
     def __init__(self, venv, width=640, height=480, camera="top", channels_first=False, depth=False,
-                 segmentation=False):
+                 segmentation=False, shadows=False, shadow_mask=False):
         torch = _torch()
         self.venv = venv
         self.width, self.height = int(width), int(height)
         if not (0 < self.width <= 4096 and 0 < self.height and self.width * self.height <= 1 << 22):
             raise ValueError(f"image {self.width}x{self.height}: width <= 4096 and width*height <= 2^22")
         scene = load_scene()
+        self.shadows = shadow_options(scene, shadows)     # before any device work
+        if shadow_mask and self.shadows is None:
+            raise ValueError("shadow_mask needs shadows")
         tri = np.ascontiguousarray(scene["tri"], dtype=np.float32)
         body = np.ascontiguousarray(scene["body"], dtype=np.int32)
         rgb = np.ascontiguousarray(scene["rgb"], dtype=np.float32)
@@ -278,6 +381,7 @@ class CameraRenderer:
         # so do the labels, read only by render_aux's label sink
         lab, _ = segment_labels(scene)
         _native.check(venv.lib.so100_render_labels(venv._handle, lab.ctypes.data, len(lab)), "so100_render_labels")
+        _upload_casters(venv, scene, self.shadows)
         self.views = None                # [N, 40] int32 device tensor of so100_view records, or None: one camera
         self.camera_name = camera
         self.camera = make_camera(scene, camera)
@@ -289,6 +393,8 @@ class CameraRenderer:
                                  device=venv.device) if depth else None
         self.segmentation = torch.full((venv.num_envs, self.height, self.width), SEG_BACKGROUND, dtype=torch.uint8,
                                        device=venv.device) if segmentation else None
+        self.shadow = torch.zeros(venv.num_envs, self.height, self.width, dtype=torch.uint8,
+                                  device=venv.device) if shadow_mask else None
 
     def identity_views(self):
         """Set ``views`` to the base view in every env (the renderer's camera, the scene's lights and colours): the
@@ -319,7 +425,7 @@ class CameraRenderer:
                                                _native.ptr(self.views), v._stream()), "so100_views_sample")
         return self.views
 
-    def render(self, qpos=None, out=None, mask=None, flat=None, views=None, depth=None, segmentation=None):
+    def render(self, qpos=None, out=None, mask=None, flat=None, views=None, depth=None, segmentation=None, shadow=None):
         """Enqueue the render of qpos (default: the env's state) into out (default self.pixels); mask: [N]
         bool/uint8 device tensor of the envs to draw (the others keep their previous image and flat row).
 
@@ -333,7 +439,10 @@ class CameraRenderer:
 
         depth, segmentation: contiguous [N, H, W] device tensors, float32 and uint8 (defaults ``self.depth`` and
         ``self.segmentation``); when there is either, the launch is so100_render_aux and fills them with the image,
-        otherwise every call is the one of a renderer without them."""
+        otherwise every call is the one of a renderer without them.
+
+        shadow: a contiguous uint8 [N, H, W] device tensor (default ``self.shadow``) for the shadow mask; only a
+        renderer with ``shadows`` takes one.  Such a renderer makes every call through so100_render_shadow."""
         torch = _torch()
         v = self.venv
         q = v.qpos if qpos is None else qpos
@@ -360,7 +469,12 @@ class CameraRenderer:
             if t is not None and (t.shape != (v.num_envs, self.height, self.width) or t.dtype != dt or
                                   not t.is_contiguous() or t.device != o.device):
                 raise ValueError(what + " [N, H, W] device tensor")
-        if flat is None and not self.channels_first and vw is None and dp is None and sg is None:
+        sm = self.shadow if shadow is None else shadow
+        if sm is not None and (self.shadows is None or sm.shape != (v.num_envs, self.height, self.width) or
+                               sm.dtype != torch.uint8 or not sm.is_contiguous() or sm.device != o.device):
+            raise ValueError("shadow must be a contiguous uint8 [N, H, W] device tensor, of a renderer with shadows")
+        if flat is None and not self.channels_first and vw is None and dp is None and sg is None and \
+                self.shadows is None:
             _native.check(v.lib.so100_render(v._handle, _native.ptr(q), _native.ptr(m), ctypes.byref(self.camera),
                                              self.width, self.height, _native.ptr(o), v._stream()), "so100_render")
             return o
@@ -373,6 +487,16 @@ class CameraRenderer:
         sinks = _native.SO100ImageOut(hwc=None if self.channels_first else _native.ptr(o),
                                       chw=_native.ptr(o) if self.channels_first else None,
                                       flat=_native.ptr(flat), flat_pitch=pitch)
+        if self.shadows is not None:
+            # K = 1 of the launch over (env, camera): [N, ...] is [N, 1, ...] and [N, 40] records are [1, N, 40]
+            aux = _native.SO100AuxOut(depth=_native.ptr(dp), label=_native.ptr(sg))
+            cams = _native.SO100Cams([self.camera], [0])
+            self.shadows.shadow_out = _native.ptr(sm)
+            _native.check(v.lib.so100_render_shadow(v._handle, _native.ptr(q), _native.ptr(m), ctypes.byref(cams),
+                                                    _native.ptr(vw), self.width, self.height, ctypes.byref(sinks),
+                                                    ctypes.byref(aux), ctypes.byref(self.shadows), v._stream()),
+                          "so100_render_shadow")
+            return o
         if dp is not None or sg is not None:
             aux = _native.SO100AuxOut(depth=_native.ptr(dp), label=_native.ptr(sg))
             _native.check(v.lib.so100_render_aux(v._handle, _native.ptr(q), _native.ptr(m), ctypes.byref(self.camera),
@@ -398,10 +522,13 @@ class MultiCameraRenderer:
     ``pixels`` is uint8 [N,K,H,W,3], with channels_first [N,K,3,H,W] (its free reshape [N,3K,H,W] is the channel-stacked
     image a CNN takes); ``depth`` float32 and ``segmentation`` uint8 are [N,K,H,W]; ``views`` is [K,N,40], camera-major,
     so that each camera's records are the contiguous [N,40] array so100_views_sample fills.  A mounted camera's records
-    hold pos (and mat) in its body's frame: camera jitter is then a mount tolerance."""
+    hold pos (and mat) in its body's frame: camera jitter is then a mount tolerance.
+
+    shadows, shadow_mask: as CameraRenderer's; the launch is then ``so100_render_shadow`` (each (env, camera) block builds
+    the map for itself) and ``shadow`` is uint8 [N,K,H,W]."""
 
     def __init__(self, venv, width=640, height=480, cameras=("top", "angle", "front_close"), channels_first=False,
-                 depth=False, segmentation=False):
+                 depth=False, segmentation=False, shadows=False, shadow_mask=False):
         torch = _torch()
         self.venv = venv
         self.width, self.height = int(width), int(height)
@@ -411,6 +538,9 @@ class MultiCameraRenderer:
             raise ValueError(f"image {self.width}x{self.height} x {K} cameras: width <= 4096 and "
                              f"width*height*cameras <= 2^22")
         scene = load_scene()
+        self.shadows = shadow_options(scene, shadows)     # before any device work
+        if shadow_mask and self.shadows is None:
+            raise ValueError("shadow_mask needs shadows")
         tri = np.ascontiguousarray(scene["tri"], dtype=np.float32)
         body = np.ascontiguousarray(scene["body"], dtype=np.int32)
         rgb = np.ascontiguousarray(scene["rgb"], dtype=np.float32)
@@ -422,6 +552,7 @@ class MultiCameraRenderer:
         self.base_rgb = np.ascontiguousarray(pack_rgb8(base), dtype=np.uint32)
         lab, _ = segment_labels(scene)
         _native.check(venv.lib.so100_render_labels(venv._handle, lab.ctypes.data, len(lab)), "so100_render_labels")
+        _upload_casters(venv, scene, self.shadows)
         self.camera_names = tuple(c if isinstance(c, str) else f"camera{k}" for k, c in enumerate(names))
         self.cameras = [camera_by_name(scene, c) if isinstance(c, str) else c for c in names]
         self.frame_body = tuple(int(getattr(c, "frame_body", 0)) for c in self.cameras)
@@ -435,6 +566,7 @@ class MultiCameraRenderer:
         self.depth = torch.zeros(n, K, self.height, self.width, dtype=torch.float32, device=d) if depth else None
         self.segmentation = torch.full((n, K, self.height, self.width), SEG_BACKGROUND, dtype=torch.uint8,
                                        device=d) if segmentation else None
+        self.shadow = torch.zeros(n, K, self.height, self.width, dtype=torch.uint8, device=d) if shadow_mask else None
 
     def identity_views(self):
         """Set ``views`` to each camera's base view in every env: the images are then bit for bit those without
@@ -465,12 +597,13 @@ class MultiCameraRenderer:
                                                    _native.ptr(self.views[c]), v._stream()), "so100_views_sample")
         return self.views
 
-    def render(self, qpos=None, out=None, mask=None, flat=None, views=None, depth=None, segmentation=None):
+    def render(self, qpos=None, out=None, mask=None, flat=None, views=None, depth=None, segmentation=None, shadow=None):
         """Enqueue the one launch that draws qpos (default: the env's state) from every camera into out (default
         ``self.pixels``).  mask: [N] envs to draw, in all their cameras (the others keep every image and flat row).
         flat: contiguous float32 [N, P >= K*3HW]: floats [c*3HW, (c+1)*3HW) of row i are camera c's [H,W,3] bytes / 255.
         views: [K, N, 40] records (default ``self.views``).  depth, segmentation: [N, K, H, W] (defaults the
-        renderer's own)."""
+        renderer's own).  shadow: uint8 [N, K, H, W] for the shadow mask (default ``self.shadow``), of a renderer with
+        ``shadows`` only; such a renderer's launch is so100_render_shadow."""
         torch = _torch()
         v = self.venv
         K, H, W = self.ncam, self.height, self.width
@@ -498,6 +631,10 @@ class MultiCameraRenderer:
             if t is not None and (t.shape != (v.num_envs, K, H, W) or t.dtype != dt or not t.is_contiguous() or
                                   t.device != o.device):
                 raise ValueError(what + " [N, K, H, W] device tensor")
+        sm = self.shadow if shadow is None else shadow
+        if sm is not None and (self.shadows is None or sm.shape != (v.num_envs, K, H, W) or sm.dtype != torch.uint8 or
+                               not sm.is_contiguous() or sm.device != o.device):
+            raise ValueError("shadow must be a contiguous uint8 [N, K, H, W] device tensor, of a renderer with shadows")
         pitch = 0
         if flat is not None:
             if flat.dim() != 2 or flat.shape[0] != v.num_envs or flat.shape[1] < K * 3 * W * H or \
@@ -508,6 +645,12 @@ class MultiCameraRenderer:
                                       chw=_native.ptr(o) if self.channels_first else None,
                                       flat=_native.ptr(flat), flat_pitch=pitch)
         aux = _native.SO100AuxOut(depth=_native.ptr(dp), label=_native.ptr(sg))
+        if self.shadows is not None:
+            self.shadows.shadow_out = _native.ptr(sm)
+            _native.check(v.lib.so100_render_shadow(v._handle, _native.ptr(q), _native.ptr(m), ctypes.byref(self.cams),
+                                                    _native.ptr(vw), W, H, ctypes.byref(sinks), ctypes.byref(aux),
+                                                    ctypes.byref(self.shadows), v._stream()), "so100_render_shadow")
+            return o
         _native.check(v.lib.so100_render_cams(v._handle, _native.ptr(q), _native.ptr(m), ctypes.byref(self.cams),
                                               _native.ptr(vw), W, H, ctypes.byref(sinks), ctypes.byref(aux),
                                               v._stream()), "so100_render_cams")

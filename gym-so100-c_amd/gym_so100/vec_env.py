@@ -122,13 +122,17 @@ class SO100VecEnv:
             by one launch (render.MultiCameraRenderer), ``camera_names`` names its K axis, ``depth`` / ``segmentation``
             and the three ``final_*`` tensors gain the K axis, ``pixels_flat`` is [N, K*3HW+6] (camera c's image / 255
             in floats [c*3HW, (c+1)*3HW), agent_pos last) and domain_randomization["visual"] draws a view per camera.
+        shadows: pixel observations only (ValueError otherwise): True or a dict (render.SHADOW_KEYS) makes the scene's
+            shadow-casting light cast hard shadows in ``pixels``, ``final_pixels`` and ``pixels_flat``, drawn by the
+            one render launch (render.CameraRenderer(shadows=...)); with visual randomisation ``light_rot_deg`` moves
+            them per env.  Physics, depth and segmentation are untouched.  The default False changes no call.
     """
 
     def __init__(self, num_envs, task="so100_cube_to_bin", obs_type="so100_state", device="cuda:0", seed=0,
                  max_episode_steps=None, autoreset=True, domain_randomization=None, env_offset=0,
                  iterations=None, debug=False, solver="newton", observation_width=640, observation_height=480,
                  variant="joint", reward64=False, nsubstep=None, convex="epa", episode_stats=False, channels_first=False,
-                 flat_pixels=False, depth=False, segmentation=False, cameras=None):
+                 flat_pixels=False, depth=False, segmentation=False, cameras=None, shadows=False):
         torch = _torch()
         if obs_type not in ("so100_state", "so100_pixels_agent_pos"):
             raise NotImplementedError(f"obs_type={obs_type!r}: 'so100_state' or 'so100_pixels_agent_pos'")
@@ -140,6 +144,11 @@ class SO100VecEnv:
             raise ValueError("channels_first / flat_pixels need obs_type='so100_pixels_agent_pos'")
         if (depth or segmentation) and obs_type != "so100_pixels_agent_pos":
             raise ValueError("depth / segmentation need obs_type='so100_pixels_agent_pos'")
+        if shadows:
+            from .render import load_scene, shadow_options
+            if obs_type != "so100_pixels_agent_pos":
+                raise ValueError("shadows need obs_type='so100_pixels_agent_pos'")
+            shadow_options(load_scene(), shadows)      # its ValueErrors before any device work
         if cameras is not None:
             from .render import check_camera_names
             if obs_type != "so100_pixels_agent_pos":
@@ -221,11 +230,11 @@ class SO100VecEnv:
             if cameras is None:
                 self.renderer = CameraRenderer(self, observation_width, observation_height,
                                                channels_first=self.channels_first, depth=depth,
-                                               segmentation=segmentation)
+                                               segmentation=segmentation, shadows=shadows)
             else:
                 self.renderer = MultiCameraRenderer(self, observation_width, observation_height, cameras=cameras,
                                                     channels_first=self.channels_first, depth=depth,
-                                                    segmentation=segmentation)
+                                                    segmentation=segmentation, shadows=shadows)
                 self.camera_names = self.renderer.camera_names
             if self._visual is not None:
                 self._sample_views()

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SO100_ABI_VERSION 22  /* 22: so100_cams / so100_render_cams / so100_cams_bytes (several cameras in one render launch, cameras mounted on a body);  21: so100_render_aux / so100_aux_out / so100_render_labels / so100_aux_out_bytes (depth and segmentation images from the render launch);  20: so100_view / so100_render_views / so100_render_materials / so100_views_sample / so100_view_bytes (camera, lights and colours per env);  19: so100_render_to / so100_image_out (one render launch, several sinks: hwc, chw, flat float32);  18: env packing of the fused step (so100_set_env_packing, so100_env_packing, so100_env_order, so100_env_cost, so100_wave_cost);  17: so100_pool_stats (the fused step's contact-record pool, sized never to run out);  16: so100_source_hash;  15: the EE variant's mocap marker box collides (SO100_NGEOM 16, SO100_NPAIR 209, SO100_NCON_MAX 643, debug stride 3,922);  14: no per-env contact cap (SO100_NCON_MAX: every pair at its collider's maximum), debug stride 3,436 (SO100_DBG_OVF), ncon_dropped always 0, status -3 for a caught C++ exception;  13: so100_buffers.ep_return / ep_final / ep_accum (device-side episode statistics);  12: so100_model.convex (GJK/EPA mesh collider, MuJoCo 3.3.3 default), box-box up to 8 contacts, cube-table one convex contact;  11: so100_buffers.ncon_dropped, debug stride 160 (contact friction forces), so100_set_fused_build;  10: so100_hull_cells (MPR support lookup);  9: pad/link-hull pairs (SO100_NPAIR 191);  8: fused step kernel, so100_set_step_mode;  7: reward64 buffer;  6: Base hull + pad pairs (SO100_NPAIR 155, SO100_NHULL_ALL 10); 5: EE/mocap weld, render API */
+#define SO100_ABI_VERSION 23  /* 23: so100_shadow / so100_render_shadow / so100_render_casters / so100_shadow_bytes (cast shadows from one light, a shadow map per block);  22: so100_cams / so100_render_cams / so100_cams_bytes (several cameras in one render launch, cameras mounted on a body);  21: so100_render_aux / so100_aux_out / so100_render_labels / so100_aux_out_bytes (depth and segmentation images from the render launch);  20: so100_view / so100_render_views / so100_render_materials / so100_views_sample / so100_view_bytes (camera, lights and colours per env);  19: so100_render_to / so100_image_out (one render launch, several sinks: hwc, chw, flat float32);  18: env packing of the fused step (so100_set_env_packing, so100_env_packing, so100_env_order, so100_env_cost, so100_wave_cost);  17: so100_pool_stats (the fused step's contact-record pool, sized never to run out);  16: so100_source_hash;  15: the EE variant's mocap marker box collides (SO100_NGEOM 16, SO100_NPAIR 209, SO100_NCON_MAX 643, debug stride 3,922);  14: no per-env contact cap (SO100_NCON_MAX: every pair at its collider's maximum), debug stride 3,436 (SO100_DBG_OVF), ncon_dropped always 0, status -3 for a caught C++ exception;  13: so100_buffers.ep_return / ep_final / ep_accum (device-side episode statistics);  12: so100_model.convex (GJK/EPA mesh collider, MuJoCo 3.3.3 default), box-box up to 8 contacts, cube-table one convex contact;  11: so100_buffers.ncon_dropped, debug stride 160 (contact friction forces), so100_set_fused_build;  10: so100_hull_cells (MPR support lookup);  9: pad/link-hull pairs (SO100_NPAIR 191);  8: fused step kernel, so100_set_step_mode;  7: reward64 buffer;  6: Base hull + pad pairs (SO100_NPAIR 155, SO100_NHULL_ALL 10); 5: EE/mocap weld, render API */
 
 /* tasks (gym_so100/__init__.py:4-32 ids; single_arm.py task classes) */
 #define SO100_TASK_CUBE_TO_BIN 0          /* gym_so100/SO100CubeToBin-v0, TimeLimit 700 */
@@ -345,6 +345,34 @@ int so100_cams_bytes(void);
 int so100_render_cams(so100_env* env, const float* qpos, const uint8_t* mask, const so100_cams* cams,
                       const so100_view* views, int width, int height, const so100_image_out* out,
                       const so100_aux_out* aux, void* stream);
+
+/* ---- (ABI 23) cast shadows (scene_so100.xml:13-16: of the three directional lights the middle one, dir="-1 1 -1",
+ * keeps MuJoCo's castshadow default).  so100_render_cams with one light occluded per pixel: each block rasterises the
+ * caster triangles into an orthographic map_size x map_size depth map along the light, then a pixel whose surface point
+ * lies more than `bias` behind the map's depth takes the colour it has with that light's diffuse taken as 0.  With `full`
+ * the image of so100_render_cams and `dark` its image from the same records with light_diffuse[light] = 0, the colour
+ * sinks hold where(shadow, dark, full) bit for bit; depth and label are so100_render_cams'.  DESIGN.md §3.7. */
+#define SO100_SHADOW_MAP_MAX 64        /* map_size <= this: the map lives in LDS */
+typedef struct so100_shadow {
+  uint32_t size;        /* sizeof(so100_shadow): the callee rejects a mismatch */
+  int32_t  light;       /* the casting light, 0..nlight-1 of every camera; -1: nothing casts (the image is so100_render_cams') */
+  int32_t  map_size;    /* S, a multiple of 8 in 8..SO100_SHADOW_MAP_MAX */
+  float    center[3];   /* the map is the square of half-side `radius` about `center`, seen along the light: */
+  float    radius;      /*   u = normalize(z x d) (x if |z x d| < 1e-6), v = d x u, texel = floor((((P-center).u|v) / radius * 0.5 + 0.5) * S) */
+  float    bias;        /* metres, >= 0: occluded iff map depth < (P-center).d - bias */
+  uint8_t* shadow_out;  /* [N][K][H][W] or NULL: 1 occluded, 0 lit, background 0; no alignment asked */
+} so100_shadow;
+int so100_shadow_bytes(void);
+/* casters: host [ntri] bytes, non-zero = the triangle is drawn into the map, for the mesh of the last so100_render_mesh
+ * call (a new mesh drops them) */
+int so100_render_casters(so100_env* env, const uint8_t* caster, int ntri);
+/* so100_render_cams' arguments and refusals, plus (each before any device work, text in so100_last_error): NULL shadow
+ * or a wrong `size`, light outside -1..nlight-1 of any camera, a map_size that is no multiple of 8 in
+ * 8..SO100_SHADOW_MAP_MAX, radius not finite or <= 0, bias negative or not finite, a non-finite center, casters not
+ * uploaded.  shadow_out alone counts as a sink.  A point outside the map is lit. */
+int so100_render_shadow(so100_env* env, const float* qpos, const uint8_t* mask, const so100_cams* cams,
+                        const so100_view* views, int width, int height, const so100_image_out* out,
+                        const so100_aux_out* aux, const so100_shadow* shadow, void* stream);
 
 /* Batched sparse GoalEnv reward (env.py:341-353): out[i] = ||a_i - d_i|| < threshold ? 0 : -1. */
 int so100_goal_reward(so100_env* env, int n, const float* achieved, const float* desired, float* out,
