@@ -42,6 +42,9 @@ hipError_t launch_render_shadow(const DevModel*, const float4*, const int*, cons
                                 const uint8_t*, const uint8_t*, int, const float*, const uint8_t*, const so100_cams&,
                                 const so100_view*, int, int, int, const so100_image_out&, const so100_aux_out&,
                                 const so100_shadow&, hipStream_t);
+hipError_t launch_render_msaa(const DevModel*, const float4*, const int*, const uint32_t*, const uint8_t*, int,
+                              const float*, const uint8_t*, const so100_cams&, const so100_view*, int, int, int,
+                              const so100_image_out&, const so100_msaa&, hipStream_t);
 hipError_t launch_views_sample(const so100_view_dr&, const so100_camera&, const uint32_t*, const uint32_t*,
                                const uint8_t*, so100_view*, int, int, hipStream_t);
 hipError_t alloc_workspace(int, Workspace*);
@@ -1351,11 +1354,13 @@ static int so100_render_aux_impl(so100_env* env, const float* qpos, const uint8_
 }
 
 // the launch over (env, camera): so100_render_aux's checks, per camera where they are the camera's.  With sh it is
-// so100_render_shadow (`who` names the call in the messages): the same checks, then the shadow struct's
+// so100_render_shadow (`who` names the call in the messages): the same checks, then the shadow struct's.  With ms it is
+// so100_render_msaa (aux NULL): the same checks with the sample struct's among those the arguments alone decide
 static int cams_launch(const char* who, so100_env* env, const float* qpos, const uint8_t* mask, const so100_cams* cams,
                        const so100_view* views, int width, int height, const so100_image_out* out,
-                       const so100_aux_out* aux, const so100_shadow* sh, void* stream) {
+                       const so100_aux_out* aux, const so100_shadow* sh, void* stream, const so100_msaa* ms = nullptr) {
   // the structs' sizes first: nothing else of them is read before they are known to be this library's layout
+  if (ms && ms->size != sizeof(so100_msaa)) return size_mismatch(who, "so100_msaa", ms->size, sizeof(so100_msaa));
   if (cams && cams->size != sizeof(so100_cams)) return size_mismatch(who, "so100_cams", cams->size, sizeof(so100_cams));
   if (out && out->size != sizeof(so100_image_out))
     return size_mismatch(who, "so100_image_out", out->size, sizeof(so100_image_out));
@@ -1384,6 +1389,25 @@ static int cams_launch(const char* who, so100_env* env, const float* qpos, const
   if (width <= 0 || height <= 0 || width > 4096 || (long)width * height * K > (1L << 22))
     return bad("bad image size (width <= 4096, width*height*ncam <= 2^22)");
   if (out && out->flat && out->flat_pitch < (int64_t)3 * width * height * K) return bad("flat_pitch < ncam*3*H*W");
+  if (ms) {
+    if (ms->samples != 1 && ms->samples != 2 && ms->samples != 4) {
+      snprintf(msg, sizeof(msg), "%s: samples %d, expected 1, 2 or 4", who, ms->samples);
+      return fail(msg);
+    }
+    for (int k = 0; k < ms->samples; k++)
+      for (int j = 0; j < 2; j++)
+        if (!(std::isfinite(ms->offset[k][j]) && std::fabs(ms->offset[k][j]) < 0.5f)) {
+          snprintf(msg, sizeof(msg), "%s: offset[%d][%d] must be finite and inside (-0.5, 0.5)", who, k, j);
+          return fail(msg);
+        }
+    if (width * ms->samples > 4096) {
+      snprintf(msg, sizeof(msg), "%s: width %d * samples %d > 4096 (a band is at least one row of samples)", who,
+               width, ms->samples);
+      return fail(msg);
+    }
+    if (!out) return bad("NULL out");
+    if (!(out->hwc || out->chw || out->flat)) return bad("no colour sink (hwc, chw and flat are all NULL)");
+  }
   if (!(out && (out->hwc || out->chw || out->flat)) && !(aux && (aux->depth || aux->label)) &&
       !(sh && sh->shadow_out))
     return bad(sh ? "no sink (hwc, chw, flat, depth, label and shadow_out are all NULL)"
@@ -1426,6 +1450,13 @@ static int cams_launch(const char* who, so100_env* env, const float* qpos, const
                                                (hipStream_t)stream);
     return e == hipSuccess ? 0 : fail_hip(who, e);
   }
+  if (ms) {
+    DeviceGuard g(env->device);
+    hipError_t e = so100::launch_render_msaa(env->d_model, env->r_tri, env->r_body, env->r_rgb, env->r_mat, env->r_ntri,
+                                             qpos, mask, *cams, views, env->n, width, height, *out, *ms,
+                                             (hipStream_t)stream);
+    return e == hipSuccess ? 0 : fail_hip(who, e);
+  }
   DeviceGuard g(env->device);
   hipError_t e = so100::launch_render_cams(env->d_model, env->r_tri, env->r_body, env->r_rgb, env->r_mat, env->r_label,
                                            env->r_ntri, qpos, mask, *cams, views, env->n, width, height,
@@ -1464,6 +1495,14 @@ static int so100_render_shadow_impl(so100_env* env, const float* qpos, const uin
                                     const so100_aux_out* aux, const so100_shadow* shadow, void* stream) {
   if (!shadow) return fail("so100_render_shadow: NULL shadow");
   return cams_launch("so100_render_shadow", env, qpos, mask, cams, views, width, height, out, aux, shadow, stream);
+}
+
+static int so100_render_msaa_impl(so100_env* env, const float* qpos, const uint8_t* mask, const so100_cams* cams,
+                                  const so100_view* views, int width, int height, const so100_image_out* out,
+                                  const so100_msaa* msaa, void* stream) {
+  if (!msaa) return fail("so100_render_msaa: NULL msaa");
+  return cams_launch("so100_render_msaa", env, qpos, mask, cams, views, width, height, out, nullptr, nullptr, stream,
+                     msaa);
 }
 
 static int so100_views_sample_impl(so100_env* env, const so100_view_dr* dr, const so100_camera* cam,
@@ -1557,6 +1596,18 @@ int so100_render_shadow(so100_env* env, const float* qpos, const uint8_t* mask, 
     return so100_render_shadow_impl(env, qpos, mask, cams, views, width, height, out, aux, shadow, stream);
   } catch (...) {
     return caught("so100_render_shadow");
+  }
+}
+
+int so100_msaa_bytes(void) { return (int)sizeof(so100_msaa); }
+
+int so100_render_msaa(so100_env* env, const float* qpos, const uint8_t* mask, const so100_cams* cams,
+                      const so100_view* views, int width, int height, const so100_image_out* out,
+                      const so100_msaa* msaa, void* stream) {
+  try {
+    return so100_render_msaa_impl(env, qpos, mask, cams, views, width, height, out, msaa, stream);
+  } catch (...) {
+    return caught("so100_render_msaa");
   }
 }
 

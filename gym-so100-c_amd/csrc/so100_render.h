@@ -1,9 +1,10 @@
-// so100_render.h - the render kernel's body, shared by its six launches: so100_render.hip (the hwc image alone),
+// so100_render.h - the render kernel's body, shared by its seven launches: so100_render.hip (the hwc image alone),
 // so100_render_sinks.hip (so100_render_to's further sinks), so100_render_views.hip (so100_render_views: camera,
 // lights and colours per env), so100_render_aux.hip (so100_render_aux: the depth and label sinks, with or without
 // views), so100_render_cams.hip (so100_render_cams: the aux launch over a grid of (env, camera), with cameras that
-// ride on a body) and so100_render_shadow.hip (so100_render_shadow: the cams launch with one light occluded per pixel
-// by a shadow map the block builds in LDS).  One translation unit per kernel: with two instantiations in one unit the hwc-only kernel was scheduled
+// ride on a body), so100_render_shadow.hip (so100_render_shadow: the cams launch with one light occluded per pixel
+// by a shadow map the block builds in LDS) and so100_render_msaa.hip (so100_render_msaa: the cams launch's colour sinks
+// with S coverage samples per pixel, resolved in LDS).  One translation unit per kernel: with two instantiations in one unit the hwc-only kernel was scheduled
 // differently and measured slower.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -20,6 +21,9 @@ constexpr int kRenderThreads = 256;
 constexpr int kTilePx = 4096;           // depth-buffer pixels per band (32 KB of LDS)
 constexpr int kBigPx = 64;              // triangles with a larger band bbox go to phase B
 constexpr int kBigCap = 256;
+constexpr int kBigCapMsaa = 1024;       // so100_render_msaa's list of phase-B triangles: kBigCap wide ones, the rest
+constexpr int kWideKeys = 1024;         // a phase-B triangle of so100_render_msaa with fewer keys is drawn by one wave
+constexpr int kWave = 64;
 
 struct RenderArgs {
   const DevModel* m;
@@ -75,6 +79,15 @@ struct RenderShadowArgs : RenderCamsArgs {
   float radius;
   float bias;                           // metres: occluded iff map depth < the point's depth - bias
   uint8_t* shadow;                      // [n][ncam][height][width] or null: 1 occluded, 0 lit, background 0
+};
+// the multisampled launch (so100_render_msaa): the cams launch whose pixels hold `samples` keys, one per sample point
+// (x + 0.5 + ox[s], y + 0.5 + oy[s]); a triangle is set up and shaded once and its flat colour goes to every sample it
+// covers.  After a band's two raster phases the samples' colours are averaged per channel, round half up (an empty
+// sample is the background's 0), and the colour sinks read that byte.  depth and seg are not written (they are
+// pixel-centre quantities: so100_render_cams')  (DESIGN.md 3.7 "Anti-aliasing")
+struct RenderMsaaArgs : RenderCamsArgs {
+  int samples;                          // S: 1, 2 or 4, with width * S <= kTilePx
+  float ox[SO100_MSAA_MAX], oy[SO100_MSAA_MAX];   // the sample offsets from the pixel centre, each inside (-0.5, 0.5)
 };
 constexpr int kShadowMapMax = SO100_SHADOW_MAP_MAX;        // 16 KB of LDS
 constexpr uint32_t kShadowEmpty = 0xFFFFFFFFu;
@@ -138,14 +151,16 @@ DEV uint32_t shade(const Cam& c, int nlight, const float* cm, const float* p0, c
 template <class Args>
 DEV decltype(auto) view_source(const Args& a, const ViewLds& vl) {
   if constexpr (std::is_same<Args, RenderViewArgs>::value || std::is_same<Args, RenderAuxArgs>::value ||
-                std::is_same<Args, RenderCamsArgs>::value || std::is_same<Args, RenderShadowArgs>::value)
+                std::is_same<Args, RenderCamsArgs>::value || std::is_same<Args, RenderShadowArgs>::value ||
+                std::is_same<Args, RenderMsaaArgs>::value)
     return (vl.v);
   else return (a.cam);
 }
-// the launch's camera: the block's own of RenderCamsArgs / RenderShadowArgs, a.cam in the other four
+// the launch's camera: the block's own of RenderCamsArgs / RenderShadowArgs / RenderMsaaArgs, a.cam in the other four
 template <class Args>
 DEV const so100_camera& launch_cam(const Args& a) {
-  if constexpr (std::is_same<Args, RenderCamsArgs>::value || std::is_same<Args, RenderShadowArgs>::value)
+  if constexpr (std::is_same<Args, RenderCamsArgs>::value || std::is_same<Args, RenderShadowArgs>::value ||
+                std::is_same<Args, RenderMsaaArgs>::value)
     return a.cams[blockIdx.y];
   else return a.cam;
 }
@@ -155,13 +170,15 @@ DEV const so100_camera& launch_cam(const Args& a) {
 // Args = RenderViewArgs: the same sinks, drawn from views[env] (not referenced, vl costs the other two no LDS);
 // Args = RenderAuxArgs: those sinks and a.depth / a.seg, from views[env] or (a.views null) from a.cam through vl;
 // Args = RenderCamsArgs: the aux kernel's block per (env, camera): grid (n, ncam), see the struct;
-// Args = RenderShadowArgs: the cams kernel with the shadow map, the second key and the shadow sink, see the struct.
+// Args = RenderShadowArgs: the cams kernel with the shadow map, the second key and the shadow sink, see the struct;
+// Args = RenderMsaaArgs: the cams kernel with S keys per pixel and the resolve, see the struct.
 template <class Args>
 __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
   constexpr bool kSinks = sizeof(Args) != sizeof(RenderArgs);
   constexpr bool kView = std::is_same<Args, RenderViewArgs>::value;
   constexpr bool kShadow = std::is_same<Args, RenderShadowArgs>::value;
-  constexpr bool kCams = std::is_same<Args, RenderCamsArgs>::value || kShadow;
+  constexpr bool kMsaa = std::is_same<Args, RenderMsaaArgs>::value;
+  constexpr bool kCams = std::is_same<Args, RenderCamsArgs>::value || kShadow || kMsaa;
   constexpr bool kAux = std::is_same<Args, RenderAuxArgs>::value || kCams;
   constexpr int kColShift = kAux ? 8 : 0;                  // the colour's place in the key's lower half
   __shared__ ViewLds vl;
@@ -175,8 +192,12 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
   __shared__ ViewLds vd;
   __shared__ uint32_t smap[kShadow ? kShadowMapMax * kShadowMapMax : 1];
   __shared__ ShadowFrame sf;
-  __shared__ int big[kBigCap];
+  // the multisampled kernel lists more: with S keys per pixel the same box passes kBigPx S times sooner, and a large
+  // triangle past a list's end is left to one thread (4 KB, inside the 40 KB that keep four workgroups per CU)
+  constexpr int kCap = kMsaa ? kBigCapMsaa : kBigCap;
+  __shared__ int big[kCap];
   __shared__ int nbig;
+  __shared__ int nmid;                             // the multisampled kernel alone: its second list's length
   __shared__ float cmat[9];                        // camera frame (columns x, y, z) for this env
   const DevModel* __restrict__ m = a.m;
   const int tid = threadIdx.x, env = blockIdx.x;
@@ -334,22 +355,43 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
 
   const float th = tanf(0.5f * cv.fovy * 0.017453292519943295f);
   const float aspect = (float)W / (float)H;
-  const int band = kTilePx / W > 0 ? kTilePx / W : 1;        // rows per band
+  int band = kTilePx / W > 0 ? kTilePx / W : 1;              // rows per band
+  // the multisampled kernel alone: a pixel holds S keys, so a band is kTilePx / (W S) rows (>= 1: the entry point
+  // refuses W S > kTilePx); the extremes of the sample offsets, which widen a triangle's box of pixels
+  float oxlo = 0.f, oxhi = 0.f, oylo = 0.f, oyhi = 0.f;
+  if constexpr (kMsaa) {
+    band = max(1, kTilePx / (W * a.samples));
+    oxlo = oxhi = a.ox[0];
+    oylo = oyhi = a.oy[0];
+    for (int s = 1; s < a.samples; s++) {
+      oxlo = fminf(oxlo, a.ox[s]); oxhi = fmaxf(oxhi, a.ox[s]);
+      oylo = fminf(oylo, a.oy[s]); oyhi = fmaxf(oyhi, a.oy[s]);
+    }
+  }
   uint8_t* img = a.out + slot() * H * W * 3;              // used where a.out is not null
 
   for (int y0 = 0; y0 < H; y0 += band) {
     const int y1 = min(H, y0 + band);
     const int npx = (y1 - y0) * W;
-    for (int i = tid; i < npx; i += kRenderThreads) zb[i] = ~0ull;
+    // the multisampled kernel's keys: sample-major, plane s = zb[s * npx, (s + 1) * npx) (S npx <= kTilePx)
+    int nkey = npx;
+    if constexpr (kMsaa) nkey = npx * a.samples;
+    for (int i = tid; i < nkey; i += kRenderThreads) zb[i] = ~0ull;
     if constexpr (kShadow) {
       for (int i = tid; i < npx; i += kRenderThreads) zd[i] = ~0ull;
     }
     if (tid == 0) nbig = 0;
+    if constexpr (kMsaa) {
+      if (tid == 0) nmid = 0;
+    }
     __syncthreads();
 
     // the shadow kernel alone: the lower half of the second key of the triangle this thread has set up, its colour
     // without the casting light (setup leaves it here for raster)
     uint32_t cold = 0;
+    // the multisampled kernel alone: the samples raster visits, [slo, shi): all of them in phase A, one in phase B
+    int slo = 0, shi = 1;
+    if constexpr (kMsaa) shi = a.samples;
     // screen-space triangle: pixel x to the right, y down; depth along the camera's -z
     auto setup = [&](int t, float* sx, float* sy, float* iz, uint32_t& col, int& bx0, int& bx1, int& by0,
                      int& by1) -> bool {
@@ -380,10 +422,18 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
       if (!ok) return false;
       const float area = (sx[1] - sx[0]) * (sy[2] - sy[0]) - (sx[2] - sx[0]) * (sy[1] - sy[0]);
       if (!(fabsf(area) > 1e-12f)) return false;
-      bx0 = max(0, (int)floorf(fminf(sx[0], fminf(sx[1], sx[2])) - 0.5f));
-      bx1 = min(W - 1, (int)ceilf(fmaxf(sx[0], fmaxf(sx[1], sx[2])) - 0.5f));
-      by0 = max(y0, (int)floorf(fminf(sy[0], fminf(sy[1], sy[2])) - 0.5f));
-      by1 = min(y1 - 1, (int)ceilf(fmaxf(sy[0], fmaxf(sy[1], sy[2])) - 0.5f));
+      if constexpr (kMsaa) {
+        // every pixel one of whose samples the triangle can cover
+        bx0 = max(0, (int)floorf(fminf(sx[0], fminf(sx[1], sx[2])) - 0.5f - oxhi));
+        bx1 = min(W - 1, (int)ceilf(fmaxf(sx[0], fmaxf(sx[1], sx[2])) - 0.5f - oxlo));
+        by0 = max(y0, (int)floorf(fminf(sy[0], fminf(sy[1], sy[2])) - 0.5f - oyhi));
+        by1 = min(y1 - 1, (int)ceilf(fmaxf(sy[0], fmaxf(sy[1], sy[2])) - 0.5f - oylo));
+      } else {
+        bx0 = max(0, (int)floorf(fminf(sx[0], fminf(sx[1], sx[2])) - 0.5f));
+        bx1 = min(W - 1, (int)ceilf(fmaxf(sx[0], fmaxf(sx[1], sx[2])) - 0.5f));
+        by0 = max(y0, (int)floorf(fminf(sy[0], fminf(sy[1], sy[2])) - 0.5f));
+        by1 = min(y1 - 1, (int)ceilf(fmaxf(sy[0], fmaxf(sy[1], sy[2])) - 0.5f));
+      }
       if (bx0 > bx1 || by0 > by1) return false;
       uint32_t base;
       if constexpr (kView) base = cv.rgb[a.material[t]];
@@ -397,6 +447,25 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
     };
     // one pixel of a set-up triangle: edge functions at the pixel centre, perspective-correct depth
     auto raster = [&](const float* sx, const float* sy, const float* iz, uint32_t col, int x, int y) {
+      if constexpr (kMsaa) {
+        // the same rules at each sample point of [slo, shi), each with its own key in its plane of zb
+        for (int s = slo; s < shi; s++) {
+          const float px = (float)x + 0.5f + a.ox[s], py = (float)y + 0.5f + a.oy[s];
+          const float area = (sx[1] - sx[0]) * (sy[2] - sy[0]) - (sx[2] - sx[0]) * (sy[1] - sy[0]);
+          const float w0 = (sx[2] - sx[1]) * (py - sy[1]) - (sy[2] - sy[1]) * (px - sx[1]);
+          const float w1 = (sx[0] - sx[2]) * (py - sy[2]) - (sy[0] - sy[2]) * (px - sx[2]);
+          const float w2 = (sx[1] - sx[0]) * (py - sy[0]) - (sy[1] - sy[0]) * (px - sx[0]);
+          const float sg = area > 0.f ? 1.f : -1.f;
+          if (w0 * sg < 0.f || w1 * sg < 0.f || w2 * sg < 0.f) continue;
+          const float inv = 1.f / area;
+          const float izp = (w0 * iz[0] + w1 * iz[1] + w2 * iz[2]) * inv;
+          if (!(izp > 0.f)) continue;
+          const float depth = 1.f / izp;
+          const unsigned long long key = ((unsigned long long)__float_as_uint(depth) << 32) | col;
+          atomicMin(&zb[s * npx + (y - y0) * W + x], key);
+        }
+        return;
+      }
       const float px = (float)x + 0.5f, py = (float)y + 0.5f;
       const float area = (sx[1] - sx[0]) * (sy[2] - sy[0]) - (sx[2] - sx[0]) * (sy[1] - sy[0]);
       const float w0 = (sx[2] - sx[1]) * (py - sy[1]) - (sy[2] - sy[1]) * (px - sx[1]);
@@ -420,25 +489,82 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
       uint32_t col;
       int bx0, bx1, by0, by1;
       if (!setup(t, sx, sy, iz, col, bx0, bx1, by0, by1)) continue;
-      if ((bx1 - bx0 + 1) * (by1 - by0 + 1) > kBigPx) {
+      int boxpx = (bx1 - bx0 + 1) * (by1 - by0 + 1);
+      if constexpr (kMsaa) boxpx *= a.samples;              // the keys the triangle can touch
+      if constexpr (kMsaa) {
+        // two lists in big[]: triangles of >= kWideKeys keys from the front (all threads each), the others from the
+        // back (a wave each)
+        if (boxpx >= kWideKeys) {
+          const int k = atomicAdd(&nbig, 1);
+          if (k < kBigCap) { big[k] = t; continue; }
+        } else if (boxpx > kBigPx) {
+          const int k = atomicAdd(&nmid, 1);
+          if (k < kCap - kBigCap) { big[kCap - 1 - k] = t; continue; }
+        }
+      } else if (boxpx > kBigPx) {
         const int k = atomicAdd(&nbig, 1);
-        if (k < kBigCap) { big[k] = t; continue; }
+        if (k < kCap) { big[k] = t; continue; }
       }
       for (int y = by0; y <= by1; y++)
         for (int x = bx0; x <= bx1; x++) raster(sx, sy, iz, col, x, y);
     }
     __syncthreads();
     // ---- phase B: each large triangle with all threads over its bbox
-    const int nb = min(nbig, kBigCap);
+    int nb = min(nbig, kCap);
+    if constexpr (kMsaa) nb = min(nbig, kBigCap);           // the wide list
     for (int k = 0; k < nb; k++) {
       float sx[3], sy[3], iz[3];
       uint32_t col;
       int bx0, bx1, by0, by1;
       if (!setup(big[k], sx, sy, iz, col, bx0, bx1, by0, by1)) continue;   // uniform: same triangle
       const int bw = bx1 - bx0 + 1, cnt = bw * (by1 - by0 + 1);
+      if constexpr (kMsaa) {
+        // all threads over (sample, box pixel), the pixel fastest: a wave's atomics go to consecutive keys of one plane
+        for (int i = tid; i < cnt * a.samples; i += kRenderThreads) {
+          const int s = i / cnt, j = i - s * cnt;
+          slo = s; shi = s + 1;
+          raster(sx, sy, iz, col, bx0 + j % bw, by0 + j / bw);
+        }
+        continue;
+      }
       for (int i = tid; i < cnt; i += kRenderThreads) raster(sx, sy, iz, col, bx0 + i % bw, by0 + i / bw);
     }
+    if constexpr (kMsaa) {
+      // the other list: a triangle per wave, its lanes over (sample, box pixel).  These are a few wavefuls of keys each,
+      // and setting one up in every thread of the block costs more than drawing it
+      const int nm = min(nmid, kCap - kBigCap);
+      for (int k = tid / kWave; k < nm; k += kRenderThreads / kWave) {
+        float sx[3], sy[3], iz[3];
+        uint32_t col;
+        int bx0, bx1, by0, by1;
+        if (!setup(big[kCap - 1 - k], sx, sy, iz, col, bx0, bx1, by0, by1)) continue;   // uniform per wave
+        const int bw = bx1 - bx0 + 1, cnt = bw * (by1 - by0 + 1);
+        for (int i = tid % kWave; i < cnt * a.samples; i += kWave) {
+          const int s = i / cnt, j = i - s * cnt;
+          slo = s; shi = s + 1;
+          raster(sx, sy, iz, col, bx0 + j % bw, by0 + j / bw);
+        }
+      }
+    }
     __syncthreads();
+    if constexpr (kMsaa) {
+      // ---- the resolve: per pixel and channel (sum of the S samples' bytes + S / 2) / S, an empty sample 0.  The result
+      // goes to plane 0 as a key with the colour in its place and the upper half 0 (never the empty key), which the
+      // sinks below read as they read any band.  Thread i touches keys i, npx + i, ... alone: no barrier in between
+      const int sh = a.samples >> 1;                           // log2 S of 1, 2, 4
+      for (int i = tid; i < npx; i += kRenderThreads) {
+        uint32_t r = 0, g = 0, b = 0;
+        for (int s = 0; s < a.samples; s++) {
+          const unsigned long long key = zb[s * npx + i];
+          const uint32_t c = key == ~0ull ? 0u : (uint32_t)key >> kColShift;
+          r += c & 0xFFu; g += (c >> 8) & 0xFFu; b += (c >> 16) & 0xFFu;
+        }
+        const uint32_t h = (uint32_t)a.samples >> 1;
+        r = (r + h) >> sh; g = (g + h) >> sh; b = (b + h) >> sh;
+        zb[i] = (unsigned long long)((r | (g << 8) | (b << 16)) << kColShift);
+      }
+      __syncthreads();
+    }
     if constexpr (kShadow) {
 #pragma clang fp contract(off)
       auto dotp = [](const float* p, const float* q) { return p[0] * q[0] + p[1] * q[1] + p[2] * q[2]; };

@@ -5,8 +5,8 @@
 // MuJoCo renders with OpenGL; this is a rasteriser of our own on the same scene description: the
 // visible geoms (tools/compile_render.py: the arm's visual meshes, decimated, the table, bin and cube
 // boxes, with their colours), the camera pose and field of view, the headlight and the scene's
-// directional lights (Lambert diffuse + ambient, two-sided, flat per triangle; no specular, shadows or
-// anti-aliasing).  It reproduces what is where in the image, not MuJoCo's pixel values: parity with
+// directional lights (Lambert diffuse + ambient, two-sided, flat per triangle; no specular; this launch has
+// no shadows or anti-aliasing: so100_render_shadow.hip and so100_render_msaa.hip).  It reproduces what is where in the image, not MuJoCo's pixel values: parity with
 // MuJoCo's renderer is unpinned.
 //
 // Layout: one 256-thread workgroup per env.

@@ -96,6 +96,23 @@ class SO100Shadow(ctypes.Structure):
         self.shadow_out = shadow_out
 
 
+SO100_MSAA_MAX = 4                 # include/so100.h: the most samples per pixel of so100_render_msaa
+
+
+class SO100Msaa(ctypes.Structure):
+    """Mirror of ``so100_msaa`` (include/so100.h): the sample count and the samples' offsets from the pixel centre of one
+    ``so100_render_msaa`` launch.  ``size`` is set to the mirror's size, which the callee checks against its own."""
+    _fields_ = [("size", ctypes.c_uint32), ("samples", ctypes.c_int32),
+                ("offset", (ctypes.c_float * 2) * SO100_MSAA_MAX)]
+
+    def __init__(self, samples=1, offsets=((0.0, 0.0),)):
+        super().__init__()
+        self.size = ctypes.sizeof(SO100Msaa)
+        self.samples = int(samples)
+        for k, (x, y) in enumerate(list(offsets)[:SO100_MSAA_MAX]):
+            self.offset[k][0], self.offset[k][1] = float(x), float(y)
+
+
 SO100_NMATERIAL = 5
 
 
@@ -137,7 +154,7 @@ class NativeLibraryError(RuntimeError):
 _lib = None
 
 
-ABI_VERSION = 23         # include/so100.h SO100_ABI_VERSION
+ABI_VERSION = 24         # include/so100.h SO100_ABI_VERSION
 HULL_CELLG = 8           # SO100_HULL_CELLG
 HULL_NCELL = 6 * HULL_CELLG * HULL_CELLG
 
@@ -195,6 +212,9 @@ def load():
     lib.so100_render_shadow.argtypes = [_P, _P, _P, ctypes.POINTER(SO100Cams), _P, ctypes.c_int, ctypes.c_int,
                                         ctypes.POINTER(SO100ImageOut), ctypes.POINTER(SO100AuxOut),
                                         ctypes.POINTER(SO100Shadow), _P]
+    lib.so100_msaa_bytes.argtypes = []
+    lib.so100_render_msaa.argtypes = [_P, _P, _P, ctypes.POINTER(SO100Cams), _P, ctypes.c_int, ctypes.c_int,
+                                      ctypes.POINTER(SO100ImageOut), ctypes.POINTER(SO100Msaa), _P]
     lib.so100_hull_cells.argtypes = [_P, _P, _P, ctypes.c_int]
     lib.so100_set_fused_build.argtypes = [_P, ctypes.c_int]
     lib.so100_fused_build.argtypes = [_P, ctypes.c_int]
@@ -211,7 +231,7 @@ def load():
                "so100_env_order", "so100_env_cost", "so100_wave_cost", "so100_view_bytes", "so100_render_materials",
                "so100_render_views", "so100_views_sample", "so100_aux_out_bytes", "so100_render_labels",
                "so100_render_aux", "so100_cams_bytes", "so100_render_cams", "so100_shadow_bytes",
-               "so100_render_casters", "so100_render_shadow"):
+               "so100_render_casters", "so100_render_shadow", "so100_msaa_bytes", "so100_render_msaa"):
         getattr(lib, fn).restype = ctypes.c_int
     lib.so100_struct_sizes.argtypes = [_P, _P]
     lib.so100_struct_sizes.restype = ctypes.c_int
@@ -235,6 +255,9 @@ def load():
     if lib.so100_shadow_bytes() != ctypes.sizeof(SO100Shadow):
         raise NativeLibraryError(f"struct layout mismatch: so100_shadow {lib.so100_shadow_bytes()} vs "
                                  f"{ctypes.sizeof(SO100Shadow)}")
+    if lib.so100_msaa_bytes() != ctypes.sizeof(SO100Msaa):
+        raise NativeLibraryError(f"struct layout mismatch: so100_msaa {lib.so100_msaa_bytes()} vs "
+                                 f"{ctypes.sizeof(SO100Msaa)}")
     _lib = lib
     return lib
 
@@ -249,7 +272,7 @@ EXPORTED_SYMBOLS = ("so100_abi_version", "so100_last_error", "so100_source_hash"
                     "so100_env_cost", "so100_wave_cost", "so100_view_bytes", "so100_render_materials",
                     "so100_render_views", "so100_views_sample", "so100_aux_out_bytes", "so100_render_labels",
                     "so100_render_aux", "so100_cams_bytes", "so100_render_cams", "so100_shadow_bytes",
-                    "so100_render_casters", "so100_render_shadow")
+                    "so100_render_casters", "so100_render_shadow", "so100_msaa_bytes", "so100_render_msaa")
 
 
 def source_hash():

@@ -28,8 +28,14 @@ scene_so100.xml:13-16) per pixel by a shadow map that every block builds in LDS 
 ``so100_render_shadow``): the arm, the jaw and the cube drop hard shadows on the table, the cue a top-down image has for
 height.  ``shadow_mask=True`` also keeps ``shadow`` (uint8, 1 = occluded).
 
+Anti-aliasing: ``antialias=True`` (or 2 / 4, or a dict over ``samples`` and ``offsets``) on either renderer draws the
+colour images with that many coverage samples per pixel, as the reference scene's 4x multisampled offscreen buffer does
+(scene_so100.xml:8, offsamples="4"), resolved in LDS inside the one launch (C-ABI ``so100_render_msaa``).  Depth and
+segmentation stay pixel-centre quantities, drawn by a second, aux-only ``so100_render_cams`` launch.
+
 It is a rasteriser of its own, not MuJoCo's OpenGL pipeline: geometry and colours are the scene's, the
-pixel values are not MuJoCo's (no specular, shadow filtering, fog or anti-aliasing).
+pixel values are not MuJoCo's (no specular, shadow filtering or fog, and the sample pattern is not the GL driver's;
+DESIGN.md §3.7, §4).
 """
 import ctypes
 import json
@@ -280,6 +286,49 @@ def shadow_options(scene, shadows):
     return make_shadow(scene, **shadows)
 
 
+# the default sample patterns of so100_render_msaa, offsets from the pixel centre (every number exact in float32): the
+# rotated grid for 4 samples, the diagonal pair for 2
+AA_PATTERNS = {1: ((0.0, 0.0),),
+               2: ((-0.25, -0.25), (0.25, 0.25)),
+               4: ((-0.125, -0.375), (0.375, -0.125), (-0.375, 0.125), (0.125, 0.375))}
+AA_KEYS = ("samples", "offsets")
+
+
+def make_antialias(samples=4, offsets=None):
+    """so100_msaa for ``so100_render_msaa``: ``samples`` (1, 2 or 4) coverage samples per pixel at ``offsets`` ([samples]
+    pairs (x, y) from the pixel centre, each inside (-0.5, 0.5); default AA_PATTERNS[samples]).  ValueError for what
+    the library would refuse."""
+    if isinstance(samples, bool) or not isinstance(samples, (int, np.integer)) or int(samples) not in AA_PATTERNS:
+        raise ValueError(f"samples {samples!r}: 1, 2 or 4")
+    samples = int(samples)
+    off = np.asarray(AA_PATTERNS[samples] if offsets is None else offsets, dtype=np.float64)
+    if off.shape != (samples, 2):
+        raise ValueError(f"offsets: {samples} pairs (x, y), got shape {off.shape}")
+    if not np.all(np.isfinite(off)) or not np.all(np.abs(off.astype(np.float32)) < 0.5):
+        raise ValueError("offsets: finite numbers inside (-0.5, 0.5)")
+    return _native.SO100Msaa(samples, off.tolist())
+
+
+def antialias_options(value):
+    """The ``antialias=`` argument of the renderers and envs (no device use): False / None -> None; True -> 4 samples in
+    the default pattern; 2 or 4 -> that many in their default pattern; a dict with keys of AA_KEYS ->
+    make_antialias(**dict).  ValueError for anything else and unknown keys."""
+    if value is None or value is False:
+        return None
+    if value is True:
+        return make_antialias(4)
+    if isinstance(value, (int, np.integer)):
+        if int(value) not in (2, 4):
+            raise ValueError(f"antialias: True, False, 2, 4 or a dict with keys of {AA_KEYS}, got {value!r}")
+        return make_antialias(int(value))
+    if not isinstance(value, dict):
+        raise ValueError(f"antialias: True, False, 2, 4 or a dict with keys of {AA_KEYS}, got {value!r}")
+    unknown = set(value) - set(AA_KEYS)
+    if unknown:
+        raise ValueError(f"antialias: unknown keys {sorted(unknown)}; known: {AA_KEYS}")
+    return make_antialias(**value)
+
+
 def pack_rgb8(rgb):
     """float32 [..., 3] in [0, 1] -> packed RGB8 as so100_render_mesh packs tri_rgb (float32 x * 255 + 0.5, truncated)"""
     x = np.clip(np.asarray(rgb, dtype=np.float32), np.float32(0), np.float32(1))
@@ -355,15 +404,26 @@ class CameraRenderer:
     (SHADOW_LIGHT) is occluded per pixel by a shadow map each block builds in the render launch (C-ABI
     ``so100_render_shadow`` with K = 1; the [N,H,W,...] tensors are the same memory as [N,1,H,W,...]).  With the default
     False every call is the one of a renderer without the option.  shadow_mask: also keep ``shadow`` (uint8 [N,H,W]:
-    1 where the light is occluded, 0 where lit and on the background); needs shadows."""
+    1 where the light is occluded, 0 where lit and on the background); needs shadows.
+
+    antialias: True (4 samples, AA_PATTERNS), 2 or 4, or a dict with keys of AA_KEYS: the colour images are drawn with
+    that many coverage samples per pixel and resolved inside the launch (C-ABI ``so100_render_msaa`` with K = 1).  With
+    depth / segmentation those two tensors come from a second, aux-only ``so100_render_cams`` launch and are bit for bit
+    what they are without antialias.  Not together with shadows (ValueError).  With the default False every call is the
+    one of a renderer without the option."""
 
     def __init__(self, venv, width=640, height=480, camera="top", channels_first=False, depth=False,
-                 segmentation=False, shadows=False, shadow_mask=False):
+                 segmentation=False, shadows=False, shadow_mask=False, antialias=False):
         torch = _torch()
         self.venv = venv
         self.width, self.height = int(width), int(height)
         if not (0 < self.width <= 4096 and 0 < self.height and self.width * self.height <= 1 << 22):
             raise ValueError(f"image {self.width}x{self.height}: width <= 4096 and width*height <= 2^22")
+        self.antialias = antialias_options(antialias)     # before any device work
+        if self.antialias is not None and shadows:
+            raise ValueError("antialias with shadows: the two key arrays times the samples do not fit the band in LDS")
+        if self.antialias is not None and self.width * self.antialias.samples > 4096:
+            raise ValueError(f"antialias: width {self.width} * samples {self.antialias.samples} > 4096")
         scene = load_scene()
         self.shadows = shadow_options(scene, shadows)     # before any device work
         if shadow_mask and self.shadows is None:
@@ -442,7 +502,10 @@ class CameraRenderer:
         otherwise every call is the one of a renderer without them.
 
         shadow: a contiguous uint8 [N, H, W] device tensor (default ``self.shadow``) for the shadow mask; only a
-        renderer with ``shadows`` takes one.  Such a renderer makes every call through so100_render_shadow."""
+        renderer with ``shadows`` takes one.  Such a renderer makes every call through so100_render_shadow.
+
+        A renderer with ``antialias`` draws out and flat through so100_render_msaa and, when there is a depth or
+        segmentation tensor, those through a second launch (so100_render_cams without colour sinks)."""
         torch = _torch()
         v = self.venv
         q = v.qpos if qpos is None else qpos
@@ -474,7 +537,7 @@ class CameraRenderer:
                                sm.dtype != torch.uint8 or not sm.is_contiguous() or sm.device != o.device):
             raise ValueError("shadow must be a contiguous uint8 [N, H, W] device tensor, of a renderer with shadows")
         if flat is None and not self.channels_first and vw is None and dp is None and sg is None and \
-                self.shadows is None:
+                self.shadows is None and self.antialias is None:
             _native.check(v.lib.so100_render(v._handle, _native.ptr(q), _native.ptr(m), ctypes.byref(self.camera),
                                              self.width, self.height, _native.ptr(o), v._stream()), "so100_render")
             return o
@@ -487,6 +550,19 @@ class CameraRenderer:
         sinks = _native.SO100ImageOut(hwc=None if self.channels_first else _native.ptr(o),
                                       chw=_native.ptr(o) if self.channels_first else None,
                                       flat=_native.ptr(flat), flat_pitch=pitch)
+        if self.antialias is not None:
+            # K = 1 of the launch over (env, camera).  Depth and labels are pixel-centre quantities: a second, aux-only
+            # so100_render_cams launch draws them, bit for bit what they are without antialias
+            cams = _native.SO100Cams([self.camera], [0])
+            _native.check(v.lib.so100_render_msaa(v._handle, _native.ptr(q), _native.ptr(m), ctypes.byref(cams),
+                                                  _native.ptr(vw), self.width, self.height, ctypes.byref(sinks),
+                                                  ctypes.byref(self.antialias), v._stream()), "so100_render_msaa")
+            if dp is not None or sg is not None:
+                aux = _native.SO100AuxOut(depth=_native.ptr(dp), label=_native.ptr(sg))
+                _native.check(v.lib.so100_render_cams(v._handle, _native.ptr(q), _native.ptr(m), ctypes.byref(cams),
+                                                      _native.ptr(vw), self.width, self.height, None,
+                                                      ctypes.byref(aux), v._stream()), "so100_render_cams")
+            return o
         if self.shadows is not None:
             # K = 1 of the launch over (env, camera): [N, ...] is [N, 1, ...] and [N, 40] records are [1, N, 40]
             aux = _native.SO100AuxOut(depth=_native.ptr(dp), label=_native.ptr(sg))
@@ -525,10 +601,13 @@ class MultiCameraRenderer:
     hold pos (and mat) in its body's frame: camera jitter is then a mount tolerance.
 
     shadows, shadow_mask: as CameraRenderer's; the launch is then ``so100_render_shadow`` (each (env, camera) block builds
-    the map for itself) and ``shadow`` is uint8 [N,K,H,W]."""
+    the map for itself) and ``shadow`` is uint8 [N,K,H,W].
+
+    antialias: as CameraRenderer's: the colour images come from one ``so100_render_msaa`` launch, depth and
+    segmentation (if kept) from a second, aux-only ``so100_render_cams`` launch; not together with shadows."""
 
     def __init__(self, venv, width=640, height=480, cameras=("top", "angle", "front_close"), channels_first=False,
-                 depth=False, segmentation=False, shadows=False, shadow_mask=False):
+                 depth=False, segmentation=False, shadows=False, shadow_mask=False, antialias=False):
         torch = _torch()
         self.venv = venv
         self.width, self.height = int(width), int(height)
@@ -537,6 +616,11 @@ class MultiCameraRenderer:
         if not (0 < self.width <= 4096 and 0 < self.height and self.width * self.height * K <= 1 << 22):
             raise ValueError(f"image {self.width}x{self.height} x {K} cameras: width <= 4096 and "
                              f"width*height*cameras <= 2^22")
+        self.antialias = antialias_options(antialias)     # before any device work
+        if self.antialias is not None and shadows:
+            raise ValueError("antialias with shadows: the two key arrays times the samples do not fit the band in LDS")
+        if self.antialias is not None and self.width * self.antialias.samples > 4096:
+            raise ValueError(f"antialias: width {self.width} * samples {self.antialias.samples} > 4096")
         scene = load_scene()
         self.shadows = shadow_options(scene, shadows)     # before any device work
         if shadow_mask and self.shadows is None:
@@ -603,7 +687,8 @@ class MultiCameraRenderer:
         flat: contiguous float32 [N, P >= K*3HW]: floats [c*3HW, (c+1)*3HW) of row i are camera c's [H,W,3] bytes / 255.
         views: [K, N, 40] records (default ``self.views``).  depth, segmentation: [N, K, H, W] (defaults the
         renderer's own).  shadow: uint8 [N, K, H, W] for the shadow mask (default ``self.shadow``), of a renderer with
-        ``shadows`` only; such a renderer's launch is so100_render_shadow."""
+        ``shadows`` only; such a renderer's launch is so100_render_shadow.  A renderer with ``antialias`` draws out and
+        flat through so100_render_msaa and depth / segmentation, if any, through a second launch."""
         torch = _torch()
         v = self.venv
         K, H, W = self.ncam, self.height, self.width
@@ -645,6 +730,16 @@ class MultiCameraRenderer:
                                       chw=_native.ptr(o) if self.channels_first else None,
                                       flat=_native.ptr(flat), flat_pitch=pitch)
         aux = _native.SO100AuxOut(depth=_native.ptr(dp), label=_native.ptr(sg))
+        if self.antialias is not None:
+            # depth and labels are pixel-centre quantities: a second, aux-only so100_render_cams launch draws them
+            _native.check(v.lib.so100_render_msaa(v._handle, _native.ptr(q), _native.ptr(m), ctypes.byref(self.cams),
+                                                  _native.ptr(vw), W, H, ctypes.byref(sinks),
+                                                  ctypes.byref(self.antialias), v._stream()), "so100_render_msaa")
+            if dp is not None or sg is not None:
+                _native.check(v.lib.so100_render_cams(v._handle, _native.ptr(q), _native.ptr(m), ctypes.byref(self.cams),
+                                                      _native.ptr(vw), W, H, None, ctypes.byref(aux), v._stream()),
+                              "so100_render_cams")
+            return o
         if self.shadows is not None:
             self.shadows.shadow_out = _native.ptr(sm)
             _native.check(v.lib.so100_render_shadow(v._handle, _native.ptr(q), _native.ptr(m), ctypes.byref(self.cams),

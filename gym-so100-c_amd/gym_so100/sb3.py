@@ -34,6 +34,9 @@ image SB3's CNN takes (a free reshape of the env's [N,K,3,H,W]); the GoalEnv emi
 ``shadows=True`` (or a dict, render.SHADOW_KEYS) is forwarded to the env: the images then carry the cast shadows of the
 scene's shadow-casting light, drawn in the same launch, with no further host copy.  The shadow mask is not forwarded.
 
+``antialias=True`` (or 2 / 4, or a dict, render.AA_KEYS) is forwarded to the env: the images are then multisampled and
+resolved inside the render launch, with no further host copy.
+
 The image (or flattened) tensor reaches the host by one asynchronous copy into pinned memory and one stream
 synchronisation per step.  Two pinned buffers alternate: **the image array of an observation returned by
 ``reset()`` / ``step()`` stays valid through the next ``step()`` and is overwritten by the one after it** (SB3's
@@ -63,11 +66,14 @@ class SO100SB3VecEnv(_VecEnvBase):
 
     def __init__(self, num_envs, task="so100_cube_to_bin", device="cuda:0", seed=0, max_episode_steps=None,
                  domain_randomization=None, env_offset=0, iterations=None, solver="newton", obs_type="so100_state",
-                 observation_width=640, observation_height=480, channels_first=False, cameras=None, shadows=False):
+                 observation_width=640, observation_height=480, channels_first=False, cameras=None, shadows=False,
+                 antialias=False):
         self.pixel_obs = obs_type == "so100_pixels_agent_pos"
         kw = {}
         if shadows and not self.pixel_obs:
             raise ValueError("shadows need obs_type='so100_pixels_agent_pos'")
+        if antialias and not self.pixel_obs:
+            raise ValueError("antialias needs obs_type='so100_pixels_agent_pos'")
         if cameras is not None:
             if not self.pixel_obs:
                 raise ValueError("cameras need obs_type='so100_pixels_agent_pos'")
@@ -81,6 +87,8 @@ class SO100SB3VecEnv(_VecEnvBase):
                 kw["cameras"] = cameras
             if shadows:
                 kw["shadows"] = shadows
+            if antialias:
+                kw["antialias"] = antialias
         elif obs_type != "so100_state":
             raise NotImplementedError(f"obs_type={obs_type!r}: 'so100_state' or 'so100_pixels_agent_pos'")
         elif channels_first:

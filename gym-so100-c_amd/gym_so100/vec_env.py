@@ -126,13 +126,19 @@ class SO100VecEnv:
             shadow-casting light cast hard shadows in ``pixels``, ``final_pixels`` and ``pixels_flat``, drawn by the
             one render launch (render.CameraRenderer(shadows=...)); with visual randomisation ``light_rot_deg`` moves
             them per env.  Physics, depth and segmentation are untouched.  The default False changes no call.
+        antialias: pixel observations only (ValueError otherwise): True (4 samples), 2, 4 or a dict
+            (render.AA_KEYS): ``pixels``, ``final_pixels``, ``pixels_flat`` and masked renders are drawn with that many
+            coverage samples per pixel, resolved inside the render launch (render.CameraRenderer(antialias=...)).
+            ``depth`` / ``segmentation`` stay what they are without it, drawn by a second launch.  Not together with
+            shadows.  The default False changes no call.
     """
 
     def __init__(self, num_envs, task="so100_cube_to_bin", obs_type="so100_state", device="cuda:0", seed=0,
                  max_episode_steps=None, autoreset=True, domain_randomization=None, env_offset=0,
                  iterations=None, debug=False, solver="newton", observation_width=640, observation_height=480,
                  variant="joint", reward64=False, nsubstep=None, convex="epa", episode_stats=False, channels_first=False,
-                 flat_pixels=False, depth=False, segmentation=False, cameras=None, shadows=False):
+                 flat_pixels=False, depth=False, segmentation=False, cameras=None, shadows=False,
+                 antialias=False):
         torch = _torch()
         if obs_type not in ("so100_state", "so100_pixels_agent_pos"):
             raise NotImplementedError(f"obs_type={obs_type!r}: 'so100_state' or 'so100_pixels_agent_pos'")
@@ -149,6 +155,16 @@ class SO100VecEnv:
             if obs_type != "so100_pixels_agent_pos":
                 raise ValueError("shadows need obs_type='so100_pixels_agent_pos'")
             shadow_options(load_scene(), shadows)      # its ValueErrors before any device work
+        if antialias:
+            from .render import antialias_options
+            if obs_type != "so100_pixels_agent_pos":
+                raise ValueError("antialias needs obs_type='so100_pixels_agent_pos'")
+            if shadows:
+                raise ValueError("antialias with shadows: the two key arrays times the samples do not fit the band "
+                                 "in LDS")
+            aa = antialias_options(antialias)            # its ValueErrors before any device work
+            if aa is not None and int(observation_width) * aa.samples > 4096:
+                raise ValueError(f"antialias: width {int(observation_width)} * samples {aa.samples} > 4096")
         if cameras is not None:
             from .render import check_camera_names
             if obs_type != "so100_pixels_agent_pos":
@@ -230,11 +246,12 @@ class SO100VecEnv:
             if cameras is None:
                 self.renderer = CameraRenderer(self, observation_width, observation_height,
                                                channels_first=self.channels_first, depth=depth,
-                                               segmentation=segmentation, shadows=shadows)
+                                               segmentation=segmentation, shadows=shadows, antialias=antialias)
             else:
                 self.renderer = MultiCameraRenderer(self, observation_width, observation_height, cameras=cameras,
                                                     channels_first=self.channels_first, depth=depth,
-                                                    segmentation=segmentation, shadows=shadows)
+                                                    segmentation=segmentation, shadows=shadows,
+                                                    antialias=antialias)
                 self.camera_names = self.renderer.camera_names
             if self._visual is not None:
                 self._sample_views()

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SO100_ABI_VERSION 23  /* 23: so100_shadow / so100_render_shadow / so100_render_casters / so100_shadow_bytes (cast shadows from one light, a shadow map per block);  22: so100_cams / so100_render_cams / so100_cams_bytes (several cameras in one render launch, cameras mounted on a body);  21: so100_render_aux / so100_aux_out / so100_render_labels / so100_aux_out_bytes (depth and segmentation images from the render launch);  20: so100_view / so100_render_views / so100_render_materials / so100_views_sample / so100_view_bytes (camera, lights and colours per env);  19: so100_render_to / so100_image_out (one render launch, several sinks: hwc, chw, flat float32);  18: env packing of the fused step (so100_set_env_packing, so100_env_packing, so100_env_order, so100_env_cost, so100_wave_cost);  17: so100_pool_stats (the fused step's contact-record pool, sized never to run out);  16: so100_source_hash;  15: the EE variant's mocap marker box collides (SO100_NGEOM 16, SO100_NPAIR 209, SO100_NCON_MAX 643, debug stride 3,922);  14: no per-env contact cap (SO100_NCON_MAX: every pair at its collider's maximum), debug stride 3,436 (SO100_DBG_OVF), ncon_dropped always 0, status -3 for a caught C++ exception;  13: so100_buffers.ep_return / ep_final / ep_accum (device-side episode statistics);  12: so100_model.convex (GJK/EPA mesh collider, MuJoCo 3.3.3 default), box-box up to 8 contacts, cube-table one convex contact;  11: so100_buffers.ncon_dropped, debug stride 160 (contact friction forces), so100_set_fused_build;  10: so100_hull_cells (MPR support lookup);  9: pad/link-hull pairs (SO100_NPAIR 191);  8: fused step kernel, so100_set_step_mode;  7: reward64 buffer;  6: Base hull + pad pairs (SO100_NPAIR 155, SO100_NHULL_ALL 10); 5: EE/mocap weld, render API */
+#define SO100_ABI_VERSION 24  /* 24: so100_msaa / so100_render_msaa / so100_msaa_bytes (multisample anti-aliasing, resolved in LDS inside the render launch);  23: so100_shadow / so100_render_shadow / so100_render_casters / so100_shadow_bytes (cast shadows from one light, a shadow map per block);  22: so100_cams / so100_render_cams / so100_cams_bytes (several cameras in one render launch, cameras mounted on a body);  21: so100_render_aux / so100_aux_out / so100_render_labels / so100_aux_out_bytes (depth and segmentation images from the render launch);  20: so100_view / so100_render_views / so100_render_materials / so100_views_sample / so100_view_bytes (camera, lights and colours per env);  19: so100_render_to / so100_image_out (one render launch, several sinks: hwc, chw, flat float32);  18: env packing of the fused step (so100_set_env_packing, so100_env_packing, so100_env_order, so100_env_cost, so100_wave_cost);  17: so100_pool_stats (the fused step's contact-record pool, sized never to run out);  16: so100_source_hash;  15: the EE variant's mocap marker box collides (SO100_NGEOM 16, SO100_NPAIR 209, SO100_NCON_MAX 643, debug stride 3,922);  14: no per-env contact cap (SO100_NCON_MAX: every pair at its collider's maximum), debug stride 3,436 (SO100_DBG_OVF), ncon_dropped always 0, status -3 for a caught C++ exception;  13: so100_buffers.ep_return / ep_final / ep_accum (device-side episode statistics);  12: so100_model.convex (GJK/EPA mesh collider, MuJoCo 3.3.3 default), box-box up to 8 contacts, cube-table one convex contact;  11: so100_buffers.ncon_dropped, debug stride 160 (contact friction forces), so100_set_fused_build;  10: so100_hull_cells (MPR support lookup);  9: pad/link-hull pairs (SO100_NPAIR 191);  8: fused step kernel, so100_set_step_mode;  7: reward64 buffer;  6: Base hull + pad pairs (SO100_NPAIR 155, SO100_NHULL_ALL 10); 5: EE/mocap weld, render API */
 
 /* tasks (gym_so100/__init__.py:4-32 ids; single_arm.py task classes) */
 #define SO100_TASK_CUBE_TO_BIN 0          /* gym_so100/SO100CubeToBin-v0, TimeLimit 700 */
@@ -373,6 +373,28 @@ int so100_render_casters(so100_env* env, const uint8_t* caster, int ntri);
 int so100_render_shadow(so100_env* env, const float* qpos, const uint8_t* mask, const so100_cams* cams,
                         const so100_view* views, int width, int height, const so100_image_out* out,
                         const so100_aux_out* aux, const so100_shadow* shadow, void* stream);
+
+/* ---- (ABI 24) multisample anti-aliasing (scene_so100.xml:8, <quality offsamples="4"/>: the reference renders into a
+ * 4x multisampled buffer).  so100_render_cams' colour sinks with `samples` coverage samples per pixel: sample s of pixel
+ * (x, y) is the point (x + 0.5 + offset[s][0], y + 0.5 + offset[s][1]); coverage, depth and the depth test are the
+ * rasteriser's rules at that point, a triangle is shaded once and its flat colour goes to every sample it covers, and a
+ * pixel's byte is (sum of its samples' bytes + samples / 2) / samples per channel (round half up; an empty sample is the
+ * background's 0).  The resolve runs in LDS inside the launch: W x H bytes leave the chip.  With samples = 1 and offset 0
+ * the image is so100_render_cams'.  DESIGN.md §3.7. */
+#define SO100_MSAA_MAX 4
+typedef struct so100_msaa {
+  uint32_t size;                       /* sizeof(so100_msaa): the callee rejects a mismatch */
+  int32_t  samples;                    /* 1, 2 or 4 */
+  float    offset[SO100_MSAA_MAX][2];  /* (x, y) of the first `samples` from the pixel centre, each inside (-0.5, 0.5) */
+} so100_msaa;
+int so100_msaa_bytes(void);
+/* so100_render_cams' arguments without aux (depth and labels are pixel-centre quantities: draw them with
+ * so100_render_cams, out NULL), and its refusals, plus (each before any device work, text in so100_last_error): NULL msaa
+ * or a wrong `size` (checked first), samples other than 1, 2 or 4, one of the first `samples` offsets not finite or with
+ * |o| >= 0.5, width * samples > 4096, NULL out or no colour sink in it.  Enqueued on stream, never synchronises. */
+int so100_render_msaa(so100_env* env, const float* qpos, const uint8_t* mask, const so100_cams* cams,
+                      const so100_view* views /* [ncam][N] or NULL */, int width, int height,
+                      const so100_image_out* out, const so100_msaa* msaa, void* stream);
 
 /* Batched sparse GoalEnv reward (env.py:341-353): out[i] = ||a_i - d_i|| < threshold ? 0 : -1. */
 int so100_goal_reward(so100_env* env, int n, const float* achieved, const float* desired, float* out,
