@@ -56,6 +56,9 @@ hipError_t launch_reward(const DevModel*, int, int, const float*, const float*, 
 hipError_t launch_spawn(const DevModel*, int, const uint32_t*, double*, hipStream_t);
 hipError_t launch_unnormalize(const DevModel*, int, const float*, float*, hipStream_t);
 hipError_t launch_goal_reward(const DevModel*, int, const float*, const float*, float*, hipStream_t);
+hipError_t launch_ee_action(const DevModel*, const so100_ee_ctrl&, int, const float*, const float*, const uint8_t*,
+                            float*, float*, float*, hipStream_t);
+hipError_t launch_ee_jacobian(const DevModel*, int, const float*, float*, float*, hipStream_t);
 }  // namespace so100
 
 using so100::DevModel;
@@ -119,6 +122,7 @@ struct so100_env {
   float4* d_cand = nullptr;     // the hulls' support-cell candidates (DevModel::hull_cand)
   int fused_waves = 0;          // the fused product build: 2 | 3 waves per SIMD, 0 auto (so100_set_fused_build)
   int pack = -1;                // the fused step's env packing: -1 auto, 0 off, 1 on (so100_set_env_packing)
+  int ee = 0;                   // the model's ee flag (the weld variant: so100_ee_action refuses it)
 };
 
 // An instantiated step graph can still be running when it is evicted: wait for its last replay first.
@@ -768,6 +772,7 @@ static so100_env* so100_create_impl(const so100_model* model, int n_envs, int de
   if (e != hipSuccess) { (void)hipFree(dm); (void)hipFree(dcand); fail_hip("so100_create: hipMemcpy", e); return nullptr; }
   so100_env* env = new so100_env{device, n_envs, dm, h.nsubstep, h.solver, -1, kFusedAutoMax, {}, false, {}, nullptr, SO100_TASK_CUBE_TO_BIN, 700, 0, 0, {}, 0, 0};
   env->d_cand = dcand;
+  env->ee = h.ee;
   if (const char* v = getenv("SO100_GRAPH")) env->use_graph = atoi(v) != 0;
   if (const char* v = getenv("SO100_FUSED")) env->fused = atoi(v) < 0 ? -1 : atoi(v) != 0;   // A/B: 0 split, 1 fused
   if (const char* v = getenv("SO100_FUSED_MAX")) env->fused_max = atoi(v);
@@ -1526,7 +1531,61 @@ static int so100_views_sample_impl(so100_env* env, const so100_view_dr* dr, cons
 }
 
 
+static int so100_ee_action_impl(so100_env* env, const so100_ee_ctrl* ctrl, const float* qpos, const float* action,
+                                const uint8_t* reinit, float* q_cmd, float* joint_action, float* ee_target,
+                                void* stream) {
+  if (!ctrl) return fail("so100_ee_action: NULL ctrl");
+  if (ctrl->size != sizeof(so100_ee_ctrl))
+    return size_mismatch("so100_ee_action", "so100_ee_ctrl", ctrl->size, sizeof(so100_ee_ctrl));
+  if (ctrl->iters < 1 || ctrl->iters > 8) return fail("so100_ee_action: iters outside 1..8");
+  auto positive = [](float v) { return std::isfinite(v) && v > 0.f; };
+  if (!positive(ctrl->pos_scale)) return fail("so100_ee_action: pos_scale must be finite and > 0");
+  if (!(std::isfinite(ctrl->rot_scale) && ctrl->rot_scale >= 0.f))
+    return fail("so100_ee_action: rot_scale must be finite and >= 0");
+  if (!positive(ctrl->damping)) return fail("so100_ee_action: damping must be finite and > 0");
+  if (!positive(ctrl->dq_max)) return fail("so100_ee_action: dq_max must be finite and > 0");
+  if (!positive(ctrl->lead_max)) return fail("so100_ee_action: lead_max must be finite and > 0");
+  for (int k = 0; k < 3; k++)
+    if (!(std::isfinite(ctrl->ws_lo[k]) && std::isfinite(ctrl->ws_hi[k]) && ctrl->ws_lo[k] <= ctrl->ws_hi[k]))
+      return fail("so100_ee_action: workspace box must be finite with ws_lo <= ws_hi");
+  if (!env) return fail("so100_ee_action: NULL env");
+  if (!qpos || !action || !q_cmd || !joint_action) return fail("so100_ee_action: NULL qpos, action, q_cmd or joint_action");
+  if (env->ee) return fail("so100_ee_action: the model has ee = 1 (the weld variant takes a mocap pose, not an action mode)");
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_ee_action(env->d_model, *ctrl, env->n, qpos, action, reinit, q_cmd, joint_action,
+                                         ee_target, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip("so100_ee_action", e);
+}
+
+static int so100_ee_jacobian_impl(so100_env* env, int n, const float* qpos, float* ee, float* jac, void* stream) {
+  if (!env || !qpos || !ee || !jac || n < 0) return fail("so100_ee_jacobian: bad arguments");
+  if (n == 0) return 0;
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_ee_jacobian(env->d_model, n, qpos, ee, jac, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip("so100_ee_jacobian", e);
+}
+
+
 extern "C" {
+
+int so100_ee_ctrl_bytes(void) { return (int)sizeof(so100_ee_ctrl); }
+
+int so100_ee_action(so100_env* env, const so100_ee_ctrl* ctrl, const float* qpos, const float* action,
+                    const uint8_t* reinit, float* q_cmd, float* joint_action, float* ee_target, void* stream) {
+  try {
+    return so100_ee_action_impl(env, ctrl, qpos, action, reinit, q_cmd, joint_action, ee_target, stream);
+  } catch (...) {
+    return caught("so100_ee_action");
+  }
+}
+
+int so100_ee_jacobian(so100_env* env, int n, const float* qpos, float* ee, float* jac, void* stream) {
+  try {
+    return so100_ee_jacobian_impl(env, n, qpos, ee, jac, stream);
+  } catch (...) {
+    return caught("so100_ee_jacobian");
+  }
+}
 
 int so100_view_bytes(void) { return (int)sizeof(so100_view); }
 

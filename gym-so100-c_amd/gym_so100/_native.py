@@ -113,6 +113,24 @@ class SO100Msaa(ctypes.Structure):
             self.offset[k][0], self.offset[k][1] = float(x), float(y)
 
 
+class SO100EeCtrl(ctypes.Structure):
+    """Mirror of ``so100_ee_ctrl`` (include/so100.h): the control record of one ``so100_ee_action`` launch.  ``size`` is
+    set to the mirror's size, which the callee checks against its own."""
+    _fields_ = [("size", ctypes.c_uint32), ("iters", ctypes.c_int32), ("pos_scale", ctypes.c_float),
+                ("rot_scale", ctypes.c_float), ("damping", ctypes.c_float), ("dq_max", ctypes.c_float),
+                ("lead_max", ctypes.c_float), ("ws_lo", ctypes.c_float * 3), ("ws_hi", ctypes.c_float * 3)]
+
+    def __init__(self, iters=2, pos_scale=0.01, rot_scale=0.17453292, damping=0.02, dq_max=0.2, lead_max=0.5,
+                 ws_lo=(0.0, 0.0, 0.0), ws_hi=(0.0, 0.0, 0.0)):
+        super().__init__()
+        self.size = ctypes.sizeof(SO100EeCtrl)
+        self.iters = int(iters)
+        self.pos_scale, self.rot_scale, self.damping = float(pos_scale), float(rot_scale), float(damping)
+        self.dq_max, self.lead_max = float(dq_max), float(lead_max)
+        self.ws_lo[:] = [float(x) for x in ws_lo]
+        self.ws_hi[:] = [float(x) for x in ws_hi]
+
+
 SO100_NMATERIAL = 5
 
 
@@ -154,7 +172,7 @@ class NativeLibraryError(RuntimeError):
 _lib = None
 
 
-ABI_VERSION = 24         # include/so100.h SO100_ABI_VERSION
+ABI_VERSION = 25         # include/so100.h SO100_ABI_VERSION
 HULL_CELLG = 8           # SO100_HULL_CELLG
 HULL_NCELL = 6 * HULL_CELLG * HULL_CELLG
 
@@ -215,6 +233,9 @@ def load():
     lib.so100_msaa_bytes.argtypes = []
     lib.so100_render_msaa.argtypes = [_P, _P, _P, ctypes.POINTER(SO100Cams), _P, ctypes.c_int, ctypes.c_int,
                                       ctypes.POINTER(SO100ImageOut), ctypes.POINTER(SO100Msaa), _P]
+    lib.so100_ee_ctrl_bytes.argtypes = []
+    lib.so100_ee_action.argtypes = [_P, ctypes.POINTER(SO100EeCtrl), _P, _P, _P, _P, _P, _P, _P]
+    lib.so100_ee_jacobian.argtypes = [_P, ctypes.c_int, _P, _P, _P, _P]
     lib.so100_hull_cells.argtypes = [_P, _P, _P, ctypes.c_int]
     lib.so100_set_fused_build.argtypes = [_P, ctypes.c_int]
     lib.so100_fused_build.argtypes = [_P, ctypes.c_int]
@@ -231,7 +252,8 @@ def load():
                "so100_env_order", "so100_env_cost", "so100_wave_cost", "so100_view_bytes", "so100_render_materials",
                "so100_render_views", "so100_views_sample", "so100_aux_out_bytes", "so100_render_labels",
                "so100_render_aux", "so100_cams_bytes", "so100_render_cams", "so100_shadow_bytes",
-               "so100_render_casters", "so100_render_shadow", "so100_msaa_bytes", "so100_render_msaa"):
+               "so100_render_casters", "so100_render_shadow", "so100_msaa_bytes", "so100_render_msaa",
+               "so100_ee_ctrl_bytes", "so100_ee_action", "so100_ee_jacobian"):
         getattr(lib, fn).restype = ctypes.c_int
     lib.so100_struct_sizes.argtypes = [_P, _P]
     lib.so100_struct_sizes.restype = ctypes.c_int
@@ -258,6 +280,9 @@ def load():
     if lib.so100_msaa_bytes() != ctypes.sizeof(SO100Msaa):
         raise NativeLibraryError(f"struct layout mismatch: so100_msaa {lib.so100_msaa_bytes()} vs "
                                  f"{ctypes.sizeof(SO100Msaa)}")
+    if lib.so100_ee_ctrl_bytes() != ctypes.sizeof(SO100EeCtrl):
+        raise NativeLibraryError(f"struct layout mismatch: so100_ee_ctrl {lib.so100_ee_ctrl_bytes()} vs "
+                                 f"{ctypes.sizeof(SO100EeCtrl)}")
     _lib = lib
     return lib
 
@@ -272,7 +297,8 @@ EXPORTED_SYMBOLS = ("so100_abi_version", "so100_last_error", "so100_source_hash"
                     "so100_env_cost", "so100_wave_cost", "so100_view_bytes", "so100_render_materials",
                     "so100_render_views", "so100_views_sample", "so100_aux_out_bytes", "so100_render_labels",
                     "so100_render_aux", "so100_cams_bytes", "so100_render_cams", "so100_shadow_bytes",
-                    "so100_render_casters", "so100_render_shadow", "so100_msaa_bytes", "so100_render_msaa")
+                    "so100_render_casters", "so100_render_shadow", "so100_msaa_bytes", "so100_render_msaa",
+                    "so100_ee_ctrl_bytes", "so100_ee_action", "so100_ee_jacobian")
 
 
 def source_hash():

@@ -37,6 +37,9 @@ scene's shadow-casting light, drawn in the same launch, with no further host cop
 ``antialias=True`` (or 2 / 4, or a dict, render.AA_KEYS) is forwarded to the env: the images are then multisampled and
 resolved inside the render launch, with no further host copy.
 
+``action_mode="ee_delta"`` (and ``ee_control``) is forwarded to the env: the action space is then ``Box(-1, 1, (5,))``,
+the Cartesian delta (dx, dy, dz, droll, grip) a device prologue turns into the joint actions of the unchanged step.
+
 The image (or flattened) tensor reaches the host by one asynchronous copy into pinned memory and one stream
 synchronisation per step.  Two pinned buffers alternate: **the image array of an observation returned by
 ``reset()`` / ``step()`` stays valid through the next ``step()`` and is overwritten by the one after it** (SB3's
@@ -67,7 +70,7 @@ class SO100SB3VecEnv(_VecEnvBase):
     def __init__(self, num_envs, task="so100_cube_to_bin", device="cuda:0", seed=0, max_episode_steps=None,
                  domain_randomization=None, env_offset=0, iterations=None, solver="newton", obs_type="so100_state",
                  observation_width=640, observation_height=480, channels_first=False, cameras=None, shadows=False,
-                 antialias=False):
+                 antialias=False, action_mode="joint", ee_control=None):
         self.pixel_obs = obs_type == "so100_pixels_agent_pos"
         kw = {}
         if shadows and not self.pixel_obs:
@@ -93,6 +96,8 @@ class SO100SB3VecEnv(_VecEnvBase):
             raise NotImplementedError(f"obs_type={obs_type!r}: 'so100_state' or 'so100_pixels_agent_pos'")
         elif channels_first:
             raise ValueError("channels_first needs obs_type='so100_pixels_agent_pos'")
+        if action_mode != "joint" or ee_control is not None:      # the env's own checks (ValueError) apply
+            kw["action_mode"], kw["ee_control"] = action_mode, ee_control
         self.venv = SO100VecEnv(num_envs, task=task, device=device, seed=seed, max_episode_steps=max_episode_steps,
                                 autoreset=True, domain_randomization=domain_randomization, env_offset=env_offset,
                                 iterations=iterations, solver=solver, episode_stats=True, **kw)
@@ -125,7 +130,7 @@ class SO100SB3VecEnv(_VecEnvBase):
                 "desired_goal": spaces.Box(low=-np.inf, high=np.inf, shape=(3,), dtype=np.float32)})
         else:
             obs_space = obs_box
-        act_space = spaces.Box(low=-1, high=1, shape=(6,), dtype=np.float32)
+        act_space = spaces.Box(low=-1, high=1, shape=(self.venv.action_dim,), dtype=np.float32)
         if self.pixel_obs:
             self.metadata = {"render_modes": ["rgb_array"]}
             self.render_mode = "rgb_array"          # read back by SB3's VecEnv.__init__ through get_attr
@@ -157,8 +162,9 @@ class SO100SB3VecEnv(_VecEnvBase):
 
     def step_async(self, actions):
         a = np.asarray(actions, dtype=np.float32)
-        if a.shape != (self.num_envs, 6):
-            raise ValueError(f"actions must be [{self.num_envs}, 6], got {a.shape}")
+        k = self.venv.action_dim
+        if a.shape != (self.num_envs, k):
+            raise ValueError(f"actions must be [{self.num_envs}, {k}], got {a.shape}")
         self._actions = a
 
     def step_wait(self):

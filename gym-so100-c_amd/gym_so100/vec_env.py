@@ -59,6 +59,52 @@ def _hash_uniform(seed, ids, field):
     return (key >> np.uint64(40)).astype(np.float64) / float(1 << 24)
 
 
+# so100_ee_ctrl's defaults (include/so100.h): pos_scale and rot_scale are the key steps of the reference's
+# scripts/teleop_ee.py:53-64 (0.01 m, 10 degrees)
+EE_CONTROL_DEFAULTS = {"iters": 2, "pos_scale": 0.01, "rot_scale": 0.17453292, "damping": 0.02, "dq_max": 0.2,
+                       "lead_max": 0.5}
+ACTION_MODES = ("joint", "ee_delta")
+
+
+def ee_control_options(control, model=None):
+    """The checked control record of action_mode="ee_delta" as a dict (no device use): EE_CONTROL_DEFAULTS overridden
+    by `control`; with `model` the workspace box defaults to the table's x / y extent and z in [0, 0.6].  Raises
+    ValueError for what so100_ee_action refuses."""
+    c = dict(EE_CONTROL_DEFAULTS)
+    control = {} if control is None else control
+    if not isinstance(control, dict):
+        raise ValueError("ee_control: None or a dict")
+    unknown = set(control) - set(c) - {"ws_lo", "ws_hi"}
+    if unknown:
+        raise ValueError(f"ee_control: unknown keys {sorted(unknown)}; known: {sorted(c) + ['ws_lo', 'ws_hi']}")
+    c.update(control)
+    if isinstance(c["iters"], bool) or not isinstance(c["iters"], (int, np.integer)) or not 1 <= c["iters"] <= 8:
+        raise ValueError(f"ee_control: iters {c['iters']!r} outside 1..8")
+    for k in ("pos_scale", "rot_scale", "damping", "dq_max", "lead_max"):
+        try:
+            v = float(c[k])
+        except (TypeError, ValueError):
+            raise ValueError(f"ee_control: {k} {c[k]!r} is not a number") from None
+        if not np.isfinite(v) or v < 0 or (v == 0 and k != "rot_scale"):
+            raise ValueError(f"ee_control: {k} {v!r} must be finite and {'>= 0' if k == 'rot_scale' else '> 0'}")
+        c[k] = v
+    if model is not None:
+        c.setdefault("ws_lo", (float(model.table_lo[0]), float(model.table_lo[1]), 0.0))
+        c.setdefault("ws_hi", (float(model.table_hi[0]), float(model.table_hi[1]), 0.6))
+    for k in ("ws_lo", "ws_hi"):
+        if k in c:
+            try:
+                v = tuple(float(x) for x in c[k])
+            except (TypeError, ValueError):
+                raise ValueError(f"ee_control: {k} {c[k]!r} is not three numbers") from None
+            if len(v) != 3 or not all(np.isfinite(v)):
+                raise ValueError(f"ee_control: {k} {c[k]!r} is not three finite numbers")
+            c[k] = v
+    if "ws_lo" in c and "ws_hi" in c and any(lo > hi for lo, hi in zip(c["ws_lo"], c["ws_hi"])):
+        raise ValueError(f"ee_control: workspace box inverted: ws_lo {c['ws_lo']} > ws_hi {c['ws_hi']}")
+    return c
+
+
 class SO100VecEnv:
     """N parallel SO-ARM100 envs on one GPU.
 
@@ -131,6 +177,19 @@ class SO100VecEnv:
             coverage samples per pixel, resolved inside the render launch (render.CameraRenderer(antialias=...)).
             ``depth`` / ``segmentation`` stay what they are without it, drawn by a second launch.  Not together with
             shadows.  The default False changes no call.
+        action_mode: "joint" (default: six normalised joint targets, every call what it is without the argument) or
+            "ee_delta": a Cartesian action a = (dx, dy, dz, droll, grip) in [-1,1]^5 on the joint model: each step a HIP
+            prologue (csrc/so100_ee.hip, include/so100.h so100_ee_action) moves an end-effector target by
+            pos_scale * a[0:3] metres, solves the four positioning joints for it by damped least squares, turns the wrist
+            by rot_scale * a[3] and writes the six joint actions into ``actions``, which the unchanged step then takes;
+            a[4] is the gripper's joint-mode command.  ``action_dim`` is 5, ``step`` / ``set_action_buffer`` take [N,5],
+            ``ee_joint_target`` [N,5] is the commanded joint targets (radians) the next delta starts from,
+            ``ee_target`` [N,3] the last position target and ``reinit`` [N] uint8 marks the envs whose command is
+            seeded from their measured pose at the next step (set by ``reset`` and, with auto-reset, for the envs that
+            finished).  ValueError with variant="ee", which has its mocap input (``set_mocap``).
+        ee_control: None or a dict overriding EE_CONTROL_DEFAULTS (iters, pos_scale, rot_scale, damping, dq_max,
+            lead_max, ws_lo, ws_hi; the workspace box defaults to the table's x / y extent and z in [0, 0.6]); unknown
+            keys and out-of-range values raise ValueError before any device use.  action_mode="ee_delta" only.
     """
 
     def __init__(self, num_envs, task="so100_cube_to_bin", obs_type="so100_state", device="cuda:0", seed=0,
@@ -138,8 +197,17 @@ class SO100VecEnv:
                  iterations=None, debug=False, solver="newton", observation_width=640, observation_height=480,
                  variant="joint", reward64=False, nsubstep=None, convex="epa", episode_stats=False, channels_first=False,
                  flat_pixels=False, depth=False, segmentation=False, cameras=None, shadows=False,
-                 antialias=False):
+                 antialias=False, action_mode="joint", ee_control=None):
         torch = _torch()
+        if action_mode not in ACTION_MODES:
+            raise ValueError(f"action_mode {action_mode!r}: one of {ACTION_MODES}")
+        if action_mode == "ee_delta":
+            if variant == "ee":
+                raise ValueError("action_mode='ee_delta' is an action mode of the joint model; variant='ee' takes its "
+                                 "mocap pose (set_mocap)")
+            ee_control_options(ee_control)               # its ValueErrors before any device work
+        elif ee_control is not None:
+            raise ValueError("ee_control needs action_mode='ee_delta'")
         if obs_type not in ("so100_state", "so100_pixels_agent_pos"):
             raise NotImplementedError(f"obs_type={obs_type!r}: 'so100_state' or 'so100_pixels_agent_pos'")
         if task not in _native.TASKS:
@@ -204,6 +272,20 @@ class SO100VecEnv:
         self.elapsed = torch.zeros(n, dtype=i32, device=d)
         self.episode = torch.zeros(n, dtype=i32, device=d)
         self.actions = torch.zeros(n, 6, dtype=f32, device=d)
+        self.action_mode = action_mode
+        self.action_dim = 6
+        self.ee_actions = self.ee_joint_target = self.ee_target = self.reinit = None
+        self.ee_control = self._ee_ctrl = None
+        if action_mode == "ee_delta":
+            self.action_dim = 5
+            self.ee_control = ee_control_options(ee_control, self.model)
+            self._ee_ctrl = _native.SO100EeCtrl(**self.ee_control)
+            self.ee_actions = torch.zeros(n, 5, dtype=f32, device=d)        # the delta actions step() copies into
+            self.ee_joint_target = torch.zeros(n, 5, dtype=f32, device=d)   # q_cmd
+            self.ee_target = torch.zeros(n, 3, dtype=f32, device=d)
+            self.reinit = torch.ones(n, dtype=torch.uint8, device=d)        # every command starts from its env's pose
+            self._reinit_bool = self.reinit.view(torch.bool)
+            self._reinit_pending = True                                      # host side: some byte of reinit may be set
         self.obs = torch.zeros(n, NOBS, dtype=f32, device=d)
         self.reward = torch.zeros(n, dtype=f32, device=d)
         self.terminated = torch.zeros(n, dtype=torch.bool, device=d)
@@ -277,7 +359,9 @@ class SO100VecEnv:
             setattr(b, name, P(getattr(self, name)))
         if not getattr(self, "_debug_enabled", True):
             b.debug = None
-        b.action = P(self.actions) if getattr(self, "_action_ref", None) is None else P(self._action_ref)
+        # (ee_delta: the step always reads the joint actions the prologue writes; an action buffer feeds the prologue)
+        b.action = P(self.actions) if getattr(self, "_action_ref", None) is None or self._ee_ctrl is not None \
+            else P(self._action_ref)
 
     def set_mocap(self, pos, quat=None, mask=None):
         """EE variant: the mocap target pose of every env (pos [N,3], quat [N,4] wxyz; the data.mocap_pos /
@@ -379,6 +463,12 @@ class SO100VecEnv:
             mask_p = _native.ptr(self._mask)
         _native.check(self.lib.so100_reset(self._handle, ctypes.byref(self._buf), mask_p, seeds_p, self._stream()),
                       "so100_reset")
+        if self._ee_ctrl is not None:                    # the reset envs' commands start again from their fresh pose
+            if mask is None:
+                self.reinit.fill_(1)
+            else:
+                self.reinit.bitwise_or_(self._mask.ne(0).to(torch.uint8))
+            self._reinit_pending = True
         if self.renderer is not None:
             if self._visual is not None and self._visual[1]:
                 self._sample_views(None if mask is None else self._mask)
@@ -387,30 +477,36 @@ class SO100VecEnv:
         return self._observation(), info
 
     def step(self, actions):
-        """actions: [N,6] (torch tensor on any device, or numpy) in [-1, 1]."""
+        """actions: [N,6] (action_mode="ee_delta": [N,5]) (torch tensor on any device, or numpy) in [-1, 1]."""
         torch = _torch()
         if getattr(self, "_action_ref", None) is not None:
             self._action_ref = None
             self._buf.action = _native.ptr(self.actions)
+        k = self.action_dim
+        dst = self.actions if self._ee_ctrl is None else self.ee_actions
         if isinstance(actions, torch.Tensor):
-            if actions.shape != (self.num_envs, 6):
-                raise ValueError(f"actions must be [{self.num_envs}, 6], got {tuple(actions.shape)}")
+            if actions.shape != (self.num_envs, k):
+                raise ValueError(f"actions must be [{self.num_envs}, {k}], got {tuple(actions.shape)}")
             if actions.device == self.device and actions.dtype == torch.float32 and actions.is_contiguous():
-                if actions.data_ptr() != self.actions.data_ptr():
-                    self.actions.copy_(actions)
+                if actions.data_ptr() != dst.data_ptr():
+                    dst.copy_(actions)
             else:
-                self.actions.copy_(actions.to(self.device, torch.float32))
+                dst.copy_(actions.to(self.device, torch.float32))
         else:
             a = np.asarray(actions, dtype=np.float32)
-            if a.shape != (self.num_envs, 6):
-                raise ValueError(f"actions must be [{self.num_envs}, 6], got {a.shape}")
-            self.actions.copy_(torch.from_numpy(a))
+            if a.shape != (self.num_envs, k):
+                raise ValueError(f"actions must be [{self.num_envs}, {k}], got {a.shape}")
+            dst.copy_(torch.from_numpy(a))
+        if self._ee_ctrl is not None:
+            self._ee_prologue()
         if self.renderer is None:
             _native.check(self.lib.so100_step(self._handle, ctypes.byref(self._buf), self._flags, self._stream()),
                           "so100_step")
             done = self.terminated | self.truncated
         else:
             done = self._step_pixels()
+        if self._ee_ctrl is not None:
+            self._ee_epilogue()
         info = {"is_success": self.success, "diverged": self.diverged, "contact_bits": self.contact_bits,
                 "ncon_dropped": self.ncon_dropped}
         if self.autoreset:
@@ -427,13 +523,33 @@ class SO100VecEnv:
 
     def set_action_buffer(self, actions):
         """Point the kernel's action input at a resident [N,6] float32 device tensor (zero copy).
-        The tensor must stay alive until the next call; ``step()`` copies into ``self.actions``."""
+        The tensor must stay alive until the next call; ``step()`` copies into ``self.actions``.
+        action_mode="ee_delta": a [N,5] tensor, read by the prologue that fills ``self.actions``."""
         torch = _torch()
-        if actions.shape != (self.num_envs, 6) or actions.dtype != torch.float32 or not actions.is_contiguous() \
+        k = self.action_dim
+        if actions.shape != (self.num_envs, k) or actions.dtype != torch.float32 or not actions.is_contiguous() \
                 or actions.device != self.device:
-            raise ValueError("action buffer must be a contiguous float32 [N,6] tensor on the env's device")
+            raise ValueError(f"action buffer must be a contiguous float32 [N,{k}] tensor on the env's device")
         self._action_ref = actions
-        self._buf.action = _native.ptr(actions)
+        if self._ee_ctrl is None:
+            self._buf.action = _native.ptr(actions)
+
+    def _ee_prologue(self):
+        """ee_delta: the delta actions (``ee_actions`` or the action buffer) -> ``actions``, on the current stream"""
+        src = self.ee_actions if getattr(self, "_action_ref", None) is None else self._action_ref
+        P = _native.ptr
+        _native.check(self.lib.so100_ee_action(self._handle, ctypes.byref(self._ee_ctrl), P(self.qpos), P(src),
+                                               P(self.reinit), P(self.ee_joint_target), P(self.actions),
+                                               P(self.ee_target), self._stream()), "so100_ee_action")
+
+    def _ee_epilogue(self):
+        """ee_delta: after the step, mark the envs whose command starts from their pose at the next step: with
+        auto-reset the envs that just finished (their qpos is a new episode's), else none"""
+        if self.autoreset:
+            _torch().logical_or(self.terminated, self.truncated, out=self._reinit_bool)
+        elif self._reinit_pending:
+            self.reinit.zero_()
+            self._reinit_pending = False
 
     def _step_pixels(self):
         """Pixel observations: step without the in-kernel reset, draw the terminal images of finished envs,
@@ -485,7 +601,13 @@ class SO100VecEnv:
 
     def step_async_raw(self):
         """Launch one env step on the current stream using the actions already in ``self.actions``
-        (no argument handling, no output views) — the benchmark's hot loop."""
+        (no argument handling, no output views) — the benchmark's hot loop.  action_mode="ee_delta": the delta
+        actions already in ``self.ee_actions`` (or the action buffer), through the prologue."""
+        if self._ee_ctrl is not None:
+            self._ee_prologue()
+            self.lib.so100_step(self._handle, ctypes.byref(self._buf), self._flags, self._stream())
+            self._ee_epilogue()
+            return
         self.lib.so100_step(self._handle, ctypes.byref(self._buf), self._flags, self._stream())
 
     def _observation(self):
@@ -516,11 +638,25 @@ class SO100VecEnv:
 
     # state access (checkpoint / teacher-forced parity tests)
     def get_state(self):
-        return {"qpos": self.qpos.clone(), "qvel": self.qvel.clone(), "qacc_warmstart": self.qacc_warmstart.clone(),
-                "elapsed": self.elapsed.clone(), "episode": self.episode.clone()}
+        st = {"qpos": self.qpos.clone(), "qvel": self.qvel.clone(), "qacc_warmstart": self.qacc_warmstart.clone(),
+              "elapsed": self.elapsed.clone(), "episode": self.episode.clone()}
+        if self._ee_ctrl is not None:
+            st["ee_joint_target"] = self.ee_joint_target.clone()
+        return st
 
-    def set_state(self, qpos, qvel, qacc_warmstart=None, elapsed=None, episode=None):
+    def set_state(self, qpos, qvel, qacc_warmstart=None, elapsed=None, episode=None, ee_joint_target=None):
+        """action_mode="ee_delta": ee_joint_target [N,5] restores the commanded joint targets (from ``get_state``);
+        without it every command starts again from the new qpos.  ValueError in joint mode."""
         torch = _torch()
+        if ee_joint_target is not None and self._ee_ctrl is None:
+            raise ValueError("ee_joint_target needs action_mode='ee_delta'")
+        if self._ee_ctrl is not None:
+            if ee_joint_target is None:
+                self.reinit.fill_(1)
+            else:
+                self.ee_joint_target.copy_(torch.as_tensor(ee_joint_target, dtype=torch.float32))
+                self.reinit.zero_()
+            self._reinit_pending = True
         self.qpos.copy_(torch.as_tensor(qpos, dtype=torch.float32))
         self.qvel.copy_(torch.as_tensor(qvel, dtype=torch.float32))
         if qacc_warmstart is not None:

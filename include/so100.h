@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SO100_ABI_VERSION 24  /* 24: so100_msaa / so100_render_msaa / so100_msaa_bytes (multisample anti-aliasing, resolved in LDS inside the render launch);  23: so100_shadow / so100_render_shadow / so100_render_casters / so100_shadow_bytes (cast shadows from one light, a shadow map per block);  22: so100_cams / so100_render_cams / so100_cams_bytes (several cameras in one render launch, cameras mounted on a body);  21: so100_render_aux / so100_aux_out / so100_render_labels / so100_aux_out_bytes (depth and segmentation images from the render launch);  20: so100_view / so100_render_views / so100_render_materials / so100_views_sample / so100_view_bytes (camera, lights and colours per env);  19: so100_render_to / so100_image_out (one render launch, several sinks: hwc, chw, flat float32);  18: env packing of the fused step (so100_set_env_packing, so100_env_packing, so100_env_order, so100_env_cost, so100_wave_cost);  17: so100_pool_stats (the fused step's contact-record pool, sized never to run out);  16: so100_source_hash;  15: the EE variant's mocap marker box collides (SO100_NGEOM 16, SO100_NPAIR 209, SO100_NCON_MAX 643, debug stride 3,922);  14: no per-env contact cap (SO100_NCON_MAX: every pair at its collider's maximum), debug stride 3,436 (SO100_DBG_OVF), ncon_dropped always 0, status -3 for a caught C++ exception;  13: so100_buffers.ep_return / ep_final / ep_accum (device-side episode statistics);  12: so100_model.convex (GJK/EPA mesh collider, MuJoCo 3.3.3 default), box-box up to 8 contacts, cube-table one convex contact;  11: so100_buffers.ncon_dropped, debug stride 160 (contact friction forces), so100_set_fused_build;  10: so100_hull_cells (MPR support lookup);  9: pad/link-hull pairs (SO100_NPAIR 191);  8: fused step kernel, so100_set_step_mode;  7: reward64 buffer;  6: Base hull + pad pairs (SO100_NPAIR 155, SO100_NHULL_ALL 10); 5: EE/mocap weld, render API */
+#define SO100_ABI_VERSION 25  /* 25: so100_ee_ctrl / so100_ee_action / so100_ee_jacobian / so100_ee_ctrl_bytes (Cartesian end-effector action mode: a batched damped least-squares prologue in front of so100_step);  24: so100_msaa / so100_render_msaa / so100_msaa_bytes (multisample anti-aliasing, resolved in LDS inside the render launch);  23: so100_shadow / so100_render_shadow / so100_render_casters / so100_shadow_bytes (cast shadows from one light, a shadow map per block);  22: so100_cams / so100_render_cams / so100_cams_bytes (several cameras in one render launch, cameras mounted on a body);  21: so100_render_aux / so100_aux_out / so100_render_labels / so100_aux_out_bytes (depth and segmentation images from the render launch);  20: so100_view / so100_render_views / so100_render_materials / so100_views_sample / so100_view_bytes (camera, lights and colours per env);  19: so100_render_to / so100_image_out (one render launch, several sinks: hwc, chw, flat float32);  18: env packing of the fused step (so100_set_env_packing, so100_env_packing, so100_env_order, so100_env_cost, so100_wave_cost);  17: so100_pool_stats (the fused step's contact-record pool, sized never to run out);  16: so100_source_hash;  15: the EE variant's mocap marker box collides (SO100_NGEOM 16, SO100_NPAIR 209, SO100_NCON_MAX 643, debug stride 3,922);  14: no per-env contact cap (SO100_NCON_MAX: every pair at its collider's maximum), debug stride 3,436 (SO100_DBG_OVF), ncon_dropped always 0, status -3 for a caught C++ exception;  13: so100_buffers.ep_return / ep_final / ep_accum (device-side episode statistics);  12: so100_model.convex (GJK/EPA mesh collider, MuJoCo 3.3.3 default), box-box up to 8 contacts, cube-table one convex contact;  11: so100_buffers.ncon_dropped, debug stride 160 (contact friction forces), so100_set_fused_build;  10: so100_hull_cells (MPR support lookup);  9: pad/link-hull pairs (SO100_NPAIR 191);  8: fused step kernel, so100_set_step_mode;  7: reward64 buffer;  6: Base hull + pad pairs (SO100_NPAIR 155, SO100_NHULL_ALL 10); 5: EE/mocap weld, render API */
 
 /* tasks (gym_so100/__init__.py:4-32 ids; single_arm.py task classes) */
 #define SO100_TASK_CUBE_TO_BIN 0          /* gym_so100/SO100CubeToBin-v0, TimeLimit 700 */
@@ -395,6 +395,44 @@ int so100_msaa_bytes(void);
 int so100_render_msaa(so100_env* env, const float* qpos, const uint8_t* mask, const so100_cams* cams,
                       const so100_view* views /* [ncam][N] or NULL */, int width, int height,
                       const so100_image_out* out, const so100_msaa* msaa, void* stream);
+
+/* ---- (ABI 25) Cartesian end-effector action mode on the joint model: a prologue that turns an
+ * end-effector delta a = (dx, dy, dz, droll, grip) in [-1,1]^5 (clipped first) into the six normalised joint actions
+ * so100_step takes; the step itself is untouched.  The reference drives its EE scene the same way, mocap_pos moved by
+ * +-0.01 m per key (scripts/teleop_ee.py:53-64).  State: q_cmd [N,5], the last commanded targets of the five arm joints
+ * (radians): the target moves from where the last command put it, not from the sagging measured pose.  Per env, with
+ * q = qpos[0:6], ee(.) = ee_site with the five arm joints at the argument, [lo_j, hi_j] joint j's range:
+ *   1. reinit[i] != 0: q_cmd <- q[0:5];
+ *   2. p = clip(ee(q_cmd) + pos_scale a[0:3], ws_lo, ws_hi);
+ *   3. c = q_cmd[0:4]; `iters` times: e = p - ee(c); J[:,j] = axis_j x (ee - anchor_j), j = 0..3 (wrist roll and jaw do
+ *      not move ee_site); dq = J' (J J' + damping^2 I)^-1 e; dq *= dq_max / max(max|dq|, dq_max); c <- clip(c + dq, lo, hi);
+ *   4. q_cmd[0:4] <- q[0:4] + clip(c - q[0:4], -lead_max, lead_max)   (anti-windup against a blocked or unreachable target);
+ *   5. q_cmd[4] <- clip(q_cmd[4] + rot_scale a[3], lo_4, hi_4);
+ *   6. joint_action[j] = clip(2 (q_cmd[j] - lo_j) / (hi_j - lo_j) - 1, -1, 1), j < 5; joint_action[5] = a[4] (the
+ *      gripper stays the joint mode's absolute command); ee_target[i] = p.
+ * float32 throughout; every step is continuous in its inputs. */
+typedef struct so100_ee_ctrl {
+  uint32_t size;        /* sizeof(so100_ee_ctrl): the callee rejects a mismatch */
+  int32_t  iters;       /* 1..8 damped least-squares steps per call */
+  float pos_scale;      /* metres per unit of a[0:3], > 0 */
+  float rot_scale;      /* radians of wrist roll per unit of a[3], >= 0 */
+  float damping;        /* > 0 */
+  float dq_max;         /* radians, > 0: the largest joint move of one least-squares step */
+  float lead_max;       /* radians, > 0: the most q_cmd may lead the measured pose */
+  float ws_lo[3], ws_hi[3];   /* the box the target is kept in, ws_lo <= ws_hi */
+} so100_ee_ctrl;
+int so100_ee_ctrl_bytes(void);
+/* One launch on `stream`, no allocation, no synchronisation.  Nonzero (text in so100_last_error), before any device
+ * work: NULL ctrl, a wrong `size` (checked first), iters outside 1..8, a pos_scale, rot_scale, damping, dq_max or
+ * lead_max that is not finite or not positive (rot_scale may be 0), a non-finite or inverted workspace box, a NULL env,
+ * qpos, action, q_cmd or joint_action, a model with ee = 1 (the weld variant has its mocap input). */
+int so100_ee_action(so100_env* env, const so100_ee_ctrl* ctrl, const float* qpos /* [N,13] */,
+                    const float* action /* [N,5] */, const uint8_t* reinit /* [N] or NULL */,
+                    float* q_cmd /* [N,5] in/out */, float* joint_action /* [N,6] */,
+                    float* ee_target /* [N,3] or NULL */, void* stream);
+/* The kinematics of the above as a standalone op (for parity tests): qpos[n,13] -> ee[n,3] = ee_site,
+ * jac[n,3,5] = its positional Jacobian over joints 0..4 (the roll column is written: it is 0 up to rounding). */
+int so100_ee_jacobian(so100_env* env, int n, const float* qpos, float* ee, float* jac, void* stream);
 
 /* Batched sparse GoalEnv reward (env.py:341-353): out[i] = ||a_i - d_i|| < threshold ? 0 : -1. */
 int so100_goal_reward(so100_env* env, int n, const float* achieved, const float* desired, float* out,
