@@ -59,6 +59,7 @@ hipError_t launch_goal_reward(const DevModel*, int, const float*, const float*, 
 hipError_t launch_ee_action(const DevModel*, const so100_ee_ctrl&, int, const float*, const float*, const uint8_t*,
                             float*, float*, float*, hipStream_t);
 hipError_t launch_ee_jacobian(const DevModel*, int, const float*, float*, float*, hipStream_t);
+hipError_t launch_hull_support_probe(const DevModel*, int, const float*, int, int, float*, hipStream_t);
 }  // namespace so100
 
 using so100::DevModel;
@@ -725,6 +726,43 @@ static int so100_hull_cells_impl(const so100_model* model, uint32_t* cells, floa
   return nc;
 }
 
+// The block table of the cells (so100_hull_blocks; on the device behind the model, so100_device.h kHullBlkOff): cell c's
+// list as kCellBlk entries at c * kCellBlk, a list of 1..kCellBlk candidates padded with its last one, any other cell
+// (no list, or a longer one) kCellBlk entries of zero coordinates and the index kCellBlkNone.
+static void hull_blocks_build(const std::vector<uint32_t>& cells, const std::vector<float>& cand, std::vector<float>& blk) {
+  float none;
+  const uint32_t nb = so100::kCellBlkNone;
+  std::memcpy(&none, &nb, sizeof(none));
+  blk.assign(4 * cells.size() * so100::kCellBlk, 0.f);
+  for (size_t c = 0; c < cells.size(); c++) {
+    const uint32_t cnt = cells[c] & 255u, start = cells[c] >> 8;
+    for (int i = 0; i < so100::kCellBlk; i++) {
+      float* dst = &blk[4 * (c * so100::kCellBlk + i)];
+      if (cnt >= 1u && cnt <= (uint32_t)so100::kCellBlk)
+        std::memcpy(dst, &cand[4 * (size_t)(start + std::min<uint32_t>((uint32_t)i, cnt - 1u))], 4 * sizeof(float));
+      else
+        dst[3] = none;
+    }
+  }
+}
+
+static int so100_hull_blocks_impl(const so100_model* model, float* blk, int cap) {
+  if (!model) return fail("so100_hull_blocks: model is NULL");
+  for (int k = 0; k < SO100_NHULL_ALL; k++)
+    if (model->hull_start[k] < 0 || model->hull_count[k] < 1 || model->hull_start[k] + model->hull_count[k] > SO100_HULL_NVERT)
+      return fail("so100_hull_blocks: hull vertex range");
+  std::vector<uint32_t> c;
+  std::vector<float> v, b;
+  hull_cells_build(model, c, v);
+  hull_blocks_build(c, v, b);
+  const int nb = (int)(b.size() / 4);
+  if (blk) {
+    if (cap < nb) return fail("so100_hull_blocks: cap too small");
+    std::memcpy(blk, b.data(), b.size() * sizeof(float));
+  }
+  return nb;
+}
+
 static int so100_struct_sizes_impl(int* model_bytes, int* buffers_bytes) {
   if (model_bytes) *model_bytes = (int)sizeof(so100_model);
   if (buffers_bytes) *buffers_bytes = (int)sizeof(so100_buffers);
@@ -747,28 +785,25 @@ static so100_env* so100_create_impl(const so100_model* model, int n_envs, int de
   std::vector<float> hv;
   hull_cells_build(model, hc, hv);
   std::memcpy(h.hull_cells, hc.data(), sizeof(h.hull_cells));
-  // the candidate lists, then each cell's list as a fixed block of kCellBlk (padded with its last candidate;
-  // longer lists keep the list path), in one buffer
-  const size_t nlist = hv.size() / 4, ncell = hc.size();
-  std::vector<float> all(hv);
-  all.resize(4 * (nlist + ncell * so100::kCellBlk), 0.f);
-  for (size_t c = 0; c < ncell; c++) {
-    const uint32_t cnt = hc[c] & 255u, start = hc[c] >> 8;
-    for (int i = 0; i < so100::kCellBlk && cnt > 0; i++) {
-      const size_t src = start + std::min<uint32_t>((uint32_t)i, cnt - 1u);
-      std::memcpy(&all[4 * (nlist + c * so100::kCellBlk + i)], &hv[4 * src], 4 * sizeof(float));
-    }
-  }
+  // the candidate lists in their own buffer (the list path of the cells whose list is longer than a block)
+  if (hv.empty()) hv.assign(4, 0.f);
   float4* dcand = nullptr;
-  e = hipMalloc(&dcand, all.size() * sizeof(float));
-  if (e == hipSuccess) e = hipMemcpy(dcand, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice);
+  e = hipMalloc(&dcand, hv.size() * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(dcand, hv.data(), hv.size() * sizeof(float), hipMemcpyHostToDevice);
   if (e != hipSuccess) { if (dcand) (void)hipFree(dcand); fail_hip("so100_create: hull cells", e); return nullptr; }
   h.hull_cand = reinterpret_cast<const so100::float4_t*>(dcand);
-  h.hull_blk = reinterpret_cast<const so100::float4_t*>(dcand) + nlist;
+  // the model and, behind it in the same allocation, the cells' block table (kHullBlkOff: the kernel's block address
+  // is the model pointer plus a constant); the env owns the one allocation (d_model)
+  std::vector<float> blk;
+  hull_blocks_build(hc, hv, blk);
+  if (blk.size() * sizeof(float) != so100::kHullBlkTotal) { (void)hipFree(dcand); fail("so100_create: block table size"); return nullptr; }
   DevModel* dm = nullptr;
-  e = hipMalloc(&dm, sizeof(DevModel));
+  e = hipMalloc(&dm, so100::kHullBlkOff + so100::kHullBlkTotal);
   if (e != hipSuccess) { (void)hipFree(dcand); fail_hip("so100_create: hipMalloc", e); return nullptr; }
+  h.hull_blk = reinterpret_cast<const so100::float4_t*>(reinterpret_cast<const char*>(dm) + so100::kHullBlkOff);
   e = hipMemcpy(dm, &h, sizeof(DevModel), hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = hipMemcpy(reinterpret_cast<char*>(dm) + so100::kHullBlkOff, blk.data(), so100::kHullBlkTotal, hipMemcpyHostToDevice);
   if (e != hipSuccess) { (void)hipFree(dm); (void)hipFree(dcand); fail_hip("so100_create: hipMemcpy", e); return nullptr; }
   so100_env* env = new so100_env{device, n_envs, dm, h.nsubstep, h.solver, -1, kFusedAutoMax, {}, false, {}, nullptr, SO100_TASK_CUBE_TO_BIN, 700, 0, 0, {}, 0, 0};
   env->d_cand = dcand;
@@ -1565,8 +1600,36 @@ static int so100_ee_jacobian_impl(so100_env* env, int n, const float* qpos, floa
   return e == hipSuccess ? 0 : fail_hip("so100_ee_jacobian", e);
 }
 
+// the step kernels' hull support for n directions of one hull (device buffers; the null stream, waited for)
+static int so100_hull_support_probe_impl(so100_env* env, int hull, const float* dirs, int n, int use_cells, float* out) {
+  if (!env || !dirs || !out || n < 0) return fail("so100_hull_support_probe: bad arguments");
+  if (hull < 0 || hull >= SO100_NHULL_ALL) return fail("so100_hull_support_probe: hull index out of range");
+  if (use_cells < 0 || use_cells > 2) return fail("so100_hull_support_probe: use_cells must be 0, 1 or 2");
+  if (n == 0) return 0;
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_hull_support_probe(env->d_model, hull, dirs, n, use_cells, out, nullptr);
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  return e == hipSuccess ? 0 : fail_hip("so100_hull_support_probe", e);
+}
+
 
 extern "C" {
+int so100_hull_blocks(const so100_model* model, float* blk, int cap) {
+  try {
+    return so100_hull_blocks_impl(model, blk, cap);
+  } catch (...) {
+    return caught("so100_hull_blocks");
+  }
+}
+
+int so100_hull_support_probe(so100_env* env, int hull, const float* dirs, int n, int use_cells, float* out) {
+  try {
+    return so100_hull_support_probe_impl(env, hull, dirs, n, use_cells, out);
+  } catch (...) {
+    return caught("so100_hull_support_probe");
+  }
+}
+
 
 int so100_ee_ctrl_bytes(void) { return (int)sizeof(so100_ee_ctrl); }
 

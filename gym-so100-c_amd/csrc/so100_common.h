@@ -61,7 +61,8 @@ template <int CTRL, bool kMin>
 DEV void arg_best_step(float& s, int& i, float& x, float& y, float& z) {
   const float os = dpp<CTRL>(s), ox = dpp<CTRL>(x), oy = dpp<CTRL>(y), oz = dpp<CTRL>(z);
   const int oi = dppi<CTRL>(i);
-  const bool t = (kMin ? os < s : os > s) || (os == s && oi < i);
+  // (| and & on the three compares, not || and &&: the short-circuit forms compiled to two exec branches per step)
+  const bool t = (kMin ? os < s : os > s) | ((os == s) & (oi < i));
   s = t ? os : s; i = t ? oi : i; x = t ? ox : x; y = t ? oy : y; z = t ? oz : z;
 }
 // the best (max, or min with kMin) score of the 16 lanes of this DPP row, first index among ties, with its

@@ -31,7 +31,7 @@ struct MprObj {
   int hull1;                        // obj1: -1 a box, else a hull (self-collision); uniform over the wave
   int s1, n1;                       // obj1 hull vertex range
   int k, s0, n;                     // obj2: hull index, vertex range
-  bool cells;                       // hull supports through the direction cells (fused kernel) or full scans
+  int sup;                          // hull supports: kSupScan (full scans) or the fused kernel's kSupFused
 };
 constexpr float kCcdEps = 2.220446049250313e-16f;   // MuJoCo's double libccd CCD_EPS (absolute tests: see oracle)
 constexpr float kMprTol = 1e-6f;            // MuJoCo ccd_tolerance
@@ -68,7 +68,7 @@ DEV void sup_sel(MprSup& d, const MprSup& s, bool w) {
   d.id = w ? s.id : d.id;
 }
 
-// A pointer read from the model (hull_cand, hull_blk) is generic to the compiler, so its loads were flat loads,
+// A pointer read from the model (hull_cand) is generic to the compiler, so its loads were flat loads,
 // which also count on lgkmcnt: every wait for them drained the LDS traffic too.  ld_global4 makes them global.
 // (Device pass only: address spaces do not exist in the host pass of this translation unit.)
 typedef float f4v __attribute__((ext_vector_type(4)));
@@ -86,14 +86,111 @@ DEV float4 ld_global4(const float4* p, size_t i) {
 DEV float sup_score(float n0, float n1, float n2, float x, float y, float z) {
   return __builtin_fmaf(n2, z, __builtin_fmaf(n1, y, n0 * x));
 }
+// How a hull support finds its candidates: the whole hull (the split path, hull_table), or through the direction's
+// cube-map cell (the fused kernel), by one of two load chains.
+//  kSupBlock: the cell's block alone, at a fixed offset behind the model; the block says itself whether it holds the
+//    cell's list (one memory round per support).  The 2-wave build: its waves are few and the step ends with the
+//    longest narrowphase chain, which this shortens.
+//  kSupCells: the cell's entry (hull_cells), then the block through the model's hull_blk pointer.  The 3-wave builds:
+//    measured there, the one-round chain loses what it gains (profiles/hull_support_ab.txt), so they keep this one.
+constexpr int kSupScan = 0, kSupCells = 1, kSupBlock = 2;
+#ifdef SO100_FUSED2_TU
+constexpr int kSupFused = kSupBlock;
+#else
+constexpr int kSupFused = kSupCells;
+#endif
+// the cube-map cell of hull k for the direction (n0, n1, n2) (so100_hull_cells; tests/test_hull_cells.py restates
+// it), or -1 for a zero or non-finite direction (the hull is then scanned).  Selects only: nothing here branches.
+DEV int hull_cell(int k, float n0, float n1, float n2) {
+  const float a0 = fabsf(n0), a1 = fabsf(n1), a2 = fabsf(n2);
+  const bool fx = a0 >= a1 && a0 >= a2, fy = !fx && a1 >= a2;
+  const float am = fx ? a0 : fy ? a1 : a2;
+  const bool ok = am > 1e-30f && am < __builtin_inff();
+  const float as = ok ? am : 1.f;     // (the cell of a direction that has none is not used)
+  const float na = fx ? n0 : fy ? n1 : n2, nu = ok ? (fx ? n1 : n0) : 0.f, nv = ok ? ((fx || fy) ? n2 : n1) : 0.f;
+  const float g = 0.5f * (float)SO100_HULL_CELLG / as;
+  const int cu = min(max((int)((nu + as) * g), 0), SO100_HULL_CELLG - 1);
+  const int cv = min(max((int)((nv + as) * g), 0), SO100_HULL_CELLG - 1);
+  const int face = 2 * (fx ? 0 : fy ? 1 : 2) + (na >= 0.f ? 0 : 1);
+  const int cell = k * SO100_HULL_NCELL + (face * SO100_HULL_CELLG + cu) * SO100_HULL_CELLG + cv;
+  return ok ? cell : -1;
+}
+// the lane's candidate of the cell's block (the block table behind the model, kHullBlkOff): one load whose address
+// depends on nothing read from memory.  cell < 0: a kCellBlkNone entry (the load is still issued, of block 0).
+DEV float4 hull_blk_load(const DevModel* __restrict__ m, int cell, int lane) {
+  const uint32_t off = (uint32_t)kHullBlkOff + (uint32_t)max(cell, 0) * (uint32_t)kHullBlkBytes + (uint32_t)lane * 16u;
+#if defined(__HIP_DEVICE_COMPILE__)
+  const f4v v = *(const __attribute__((address_space(1))) f4v*)((const __attribute__((address_space(1))) char*)(const void*)m + off);
+#else
+  const float4 v = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(m) + off);
+#endif
+  return make_float4(v.x, v.y, v.z, cell < 0 ? __uint_as_float(kCellBlkNone) : v.w);
+}
 // first vertex of hull k (vertex range [s0, s0 + n)) maximising (n0, n1, n2) . v: lanes split the
 // candidates, then a 16-lane (score, index) max keeps the oracle's first maximal vertex; every lane of the
 // row gets it.  The candidates are those of the direction's cube-map cell (so100_hull_cells: a superset of
 // the cell's possible supports, in vertex order, so the same vertex as a scan of the whole hull, which
 // remains for a cell whose list did not fit and for a zero or non-finite direction).  The direction is
 // uniform over the row, so is the path.
-DEV float4 hull_support(const DevModel* __restrict__ m, bool cells, int k, int s0, int cnt, float n0, float n1, float n2,
-                        int lane) {   // (x, y, z, vertex index within the hull as int bits)
+// hull_support_rest: the cell's list (e: its hull_cells entry, when it has one), else the whole-hull scan.
+DEV float4 hull_support_rest(const DevModel* __restrict__ m, uint32_t e, int s0, int cnt, float n0, float n1, float n2,
+                             int lane) {   // (x, y, z, vertex index within the hull as int bits)
+  float best = -__builtin_inff(), bx = 0.f, by = 0.f, bz = 0.f;
+  int bi = 0x7fffffff;
+  const int cc = (int)(e & 255u);
+  if (cc > 0) {
+    const float4* __restrict__ cand = reinterpret_cast<const float4*>(m->hull_cand) + (e >> 8);
+    for (int base = lane; base < cc; base += 2 * kLanes) {
+      const float4 c0 = ld_global4(cand, base);
+      const float4 c1 = ld_global4(cand, min(base + kLanes, cc - 1));
+      const float s0c = sup_score(n0, n1, n2, c0.x, c0.y, c0.z);
+      if (s0c > best) { best = s0c; bi = __float_as_int(c0.w); bx = c0.x; by = c0.y; bz = c0.z; }
+      const float s1c = sup_score(n0, n1, n2, c1.x, c1.y, c1.z);
+      if (base + kLanes < cc && s1c > best) { best = s1c; bi = __float_as_int(c1.w); bx = c1.x; by = c1.y; bz = c1.z; }
+    }
+    arg_best16<false>(best, bi, bx, by, bz);
+    return make_float4(bx, by, bz, __int_as_float(bi));
+  }
+  const float4* __restrict__ verts = reinterpret_cast<const float4*>(m->hull_vert) + s0;
+  for (int base = lane; base < cnt; base += 8 * kLanes) {
+    float4 vb[8];
+#pragma unroll
+    for (int u = 0; u < 8; u++) vb[u] = verts[min(base + u * kLanes, cnt - 1)];
+#pragma unroll
+    for (int u = 0; u < 8; u++) {
+      const int i = base + u * kLanes;
+      const float sc = sup_score(n0, n1, n2, vb[u].x, vb[u].y, vb[u].z);
+      const bool t = i < cnt && sc > best;
+      best = t ? sc : best; bi = t ? i : bi;
+      bx = t ? vb[u].x : bx; by = t ? vb[u].y : by; bz = t ? vb[u].z : bz;
+    }
+  }
+  arg_best16<false>(best, bi, bx, by, bz);
+  return make_float4(bx, by, bz, __int_as_float(bi));
+}
+// kSupBlock, from the lane's entry cb of the cell's block (hull_blk_load): a block that holds the cell's list is the
+// whole support, that one load and the reduction.  Only a kCellBlkNone block goes on to the cell's entry
+// (hull_cells[cell]: its list, when it has one) or to the whole-hull scan (cell < 0: no cell).
+DEV float4 hull_support_blk(const DevModel* __restrict__ m, float4 cb, int cell, int s0, int cnt, float n0, float n1,
+                            float n2, int lane) {
+  if (__float_as_uint(cb.w) != kCellBlkNone) {
+    // lanes beyond the list hold its last candidate again: the same (score, index), the same winner
+    float best = sup_score(n0, n1, n2, cb.x, cb.y, cb.z), bx = cb.x, by = cb.y, bz = cb.z;
+    int bi = __float_as_int(cb.w);
+    arg_best16<false>(best, bi, bx, by, bz);
+    return make_float4(bx, by, bz, __int_as_float(bi));
+  }
+  return hull_support_rest(m, cell >= 0 ? m->hull_cells[cell] : 0u, s0, cnt, n0, n1, n2, lane);
+}
+// sup: kSupScan | kSupCells | kSupBlock (a constant at every call once inlined)
+DEV float4 hull_support(const DevModel* __restrict__ m, int sup, int k, int s0, int cnt, float n0, float n1, float n2,
+                        int lane) {
+  if (sup == kSupBlock) {
+    const int cell = hull_cell(k, n0, n1, n2);
+    return hull_support_blk(m, hull_blk_load(m, cell, lane), cell, s0, cnt, n0, n1, n2, lane);
+  }
+  // kSupCells and kSupScan: the cell's entry, then its block through the model's pointer (the parent chain, kept as one
+  // body: the 3-wave builds' register allocation is sensitive to its shape)
   float best = -__builtin_inff(), bx = 0.f, by = 0.f, bz = 0.f;
   int bi = 0x7fffffff;
   {
@@ -101,7 +198,7 @@ DEV float4 hull_support(const DevModel* __restrict__ m, bool cells, int k, int s
     const bool fx = a0 >= a1 && a0 >= a2, fy = !fx && a1 >= a2;
     const float am = fx ? a0 : fy ? a1 : a2;
     uint32_t e = 0u;
-    if (cells && am > 1e-30f && am < __builtin_inff()) {
+    if (sup == kSupCells && am > 1e-30f && am < __builtin_inff()) {
       const float na = fx ? n0 : fy ? n1 : n2, nu = fx ? n1 : n0, nv = (fx || fy) ? n2 : n1;
       const float g = 0.5f * (float)SO100_HULL_CELLG / am;
       const int cu = min(max((int)((nu + am) * g), 0), SO100_HULL_CELLG - 1);
@@ -178,7 +275,7 @@ DEV bool hull_table(const DevModel* __restrict__ m, const EnvShared& sh, int lan
       // position is added after (compared in world z, ~0.5 m with 3e-8 m rounding, a hull face lying nearly flat
       // tied its corners and fp32 picked another than fp64, centimetres away; round 6, oracle table_hull_fast)
       const float* R = sh.ser.xm[m->hull_body[k] - 2];
-      const float4 v = hull_support(m, false, k, m->hull_start[k], m->hull_count[k], -R[6], -R[7], -R[8], lane);
+      const float4 v = hull_support(m, kSupScan, k, m->hull_start[k], m->hull_count[k], -R[6], -R[7], -R[8], lane);
       const float hv[3] = {v.x, v.y, v.z};
       float w[3];
       mulmv3(w, R, hv);
@@ -195,6 +292,19 @@ DEV bool hull_table(const DevModel* __restrict__ m, const EnvShared& sh, int lan
 
 DEV void mpr_support(const DevModel* __restrict__ m, const MprObj& o, const float* d, MprSup& s, int lane) {
   uint32_t id = 0u;
+  // obj2's block load first (its direction and cell are known from d): in flight under obj1's support, and, for a
+  // hull obj1, beside obj1's own block load, before either reduction
+  int cell2 = -1;
+  float4 cb2 = make_float4(0.f, 0.f, 0.f, __uint_as_float(kCellBlkNone));
+#ifdef SO100_NO_SUP_PAIR   // (A/B switch: obj2's block load after obj1's support)
+  constexpr bool kEarly = false;
+#else
+  constexpr bool kEarly = true;
+#endif
+  if (o.sup == kSupBlock && kEarly) {
+    cell2 = hull_cell(o.k, -d[0], -d[1], -d[2]);
+    cb2 = hull_blk_load(m, cell2, lane);
+  }
 #pragma unroll
   for (int t = 0; t < 3; t++) s.v1[t] = o.c[t];
   if (o.hull1 < 0) {
@@ -210,14 +320,19 @@ DEV void mpr_support(const DevModel* __restrict__ m, const MprObj& o, const floa
     // obj1 hull: the direction into its body frame, its support back into H
     float dl[3], w[3];
     mulmtv3(dl, o.ax, d);
-    const float4 v = hull_support(m, o.cells, o.hull1, o.s1, o.n1, dl[0], dl[1], dl[2], lane);
+    const float4 v = hull_support(m, o.sup, o.hull1, o.s1, o.n1, dl[0], dl[1], dl[2], lane);
     const float vv[3] = {v.x, v.y, v.z};
     id = (uint32_t)__float_as_int(v.w);
     mulmv3(w, o.ax, vv);
 #pragma unroll
     for (int t = 0; t < 3; t++) s.v1[t] += w[t];
   }
-  const float4 v = hull_support(m, o.cells, o.k, o.s0, o.n, -d[0], -d[1], -d[2], lane);
+  if (o.sup == kSupBlock && !kEarly) {
+    cell2 = hull_cell(o.k, -d[0], -d[1], -d[2]);
+    cb2 = hull_blk_load(m, cell2, lane);
+  }
+  const float4 v = o.sup == kSupBlock ? hull_support_blk(m, cb2, cell2, o.s0, o.n, -d[0], -d[1], -d[2], lane)
+                                      : hull_support(m, o.sup, o.k, o.s0, o.n, -d[0], -d[1], -d[2], lane);
   s.v2[0] = v.x; s.v2[1] = v.y; s.v2[2] = v.z;
   s.id = id | (uint32_t)__float_as_int(v.w) << 10;
   sub3(s.v, s.v1, s.v2);
@@ -441,15 +556,32 @@ DEV bool mpr_penetration(const DevModel* __restrict__ m, const MprObj& o, float&
 // vertex points in registers across the row (EpaVerts).
 constexpr int kEpaMaxV = 24, kEpaMaxF = 44, kEpaMaxE = 48;   // oracle EPA_MAXV / EPA_MAXF / EPA_MAXE
 // Diagnostic build only (-DSO100_EPA_STAMPS, tools/dev/epa_stamps.py): shader cycles of the convex collider's
-// phases summed over the rows (lane 0) into a device counter array read by so100_dev_epa_cycles.
+// phases summed over the rows (lane 0) into a device counter array read by so100_dev_epa_cycles.  An item's deltas
+// add up in registers (est_) and go to the counters once, when the item ends (ESTAMP_FLUSH): an atomic between the
+// phases was part of what the next phase's stamp measured.  Each translation unit of the step kernels keeps its own
+// counters (the 2-wave build's: so100_dev_epa_cycles2); so100_dev_epa_cycles sums them.
 #ifdef SO100_EPA_STAMPS
-__device__ unsigned long long so100_epa_cyc[12];  // GJK, EPA, items, EPA items, EPA iters, support, horizon+facets, scan,
-                                                   // then inside the horizon: visibility + twins, masks, facets
+static __device__ unsigned long long so100_epa_cyc[12];  // GJK, EPA, items, EPA items, EPA iters, support, horizon+facets,
+                                                          // scan, then inside the horizon: visibility + twins, masks, facets
 #define ESTAMP_T() __builtin_amdgcn_s_memtime()
-#define ESTAMP_ADD(k, v) do { if (lane == 0) atomicAdd(&so100_epa_cyc[k], (unsigned long long)(v)); } while (0)
+#define ESTAMP_DECL unsigned long long est_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#define ESTAMP_PARAM , unsigned long long* est_
+#define ESTAMP_ARG , est_
+#define ESTAMP_ADD(k, v) do { est_[k] += (unsigned long long)(v); } while (0)
+#define ESTAMP_FLUSH()                                                                \
+  do {                                                                                \
+    if (lane == 0) {                                                                  \
+      _Pragma("unroll") for (int k_ = 0; k_ < 12; k_++)                               \
+        if (est_[k_] != 0ull) atomicAdd(&so100_epa_cyc[k_], est_[k_]);                \
+    }                                                                                 \
+  } while (0)
 #else
 #define ESTAMP_T() 0ull
+#define ESTAMP_DECL
+#define ESTAMP_PARAM
+#define ESTAMP_ARG
 #define ESTAMP_ADD(k, v) do { (void)(v); } while (0)
+#define ESTAMP_FLUSH() do {} while (0)
 #endif
 struct EpaPoly {
   float4 plane[kEpaMaxF];           // outward normal, distance from the origin
@@ -703,8 +835,8 @@ DEV bool epa_feature_witness(const DevModel* __restrict__ m, const MprObj& o, ui
 // EPA from GJK's tetrahedron (oracle epa_penetration, the same bookkeeping order): true and (depth, dir
 // geom1 -> geom2, pos) on the facet reached.  P: the row's LDS polytope; lane: 0..15 in the row.
 DEV bool epa_penetration(const DevModel* __restrict__ m, const MprObj& o, const GjkPt* S, float& depth, float* dir,
-                         float* pos, EpaPoly& P, int lane, int grp) {
-  uint64_t alive = 0ull;                        // live facet slots (row-uniform)
+                         float* pos, EpaPoly& P, int lane, int grp ESTAMP_PARAM) {
+  uint64_t alive = 0ull;                       // live facet slots (row-uniform)
   // the initial tetrahedron: faces (0,1,2), (0,3,1), (0,2,3), (1,3,2), each outward (away from the 4th vertex)
   {
     bool ok = true;
@@ -972,15 +1104,20 @@ DEV bool convex_penetration(const DevModel* __restrict__ m, const MprObj& o, flo
     for (int t = 0; t < 3; t++) S[i].v[t] = 0.f;
     S[i].id = 0u;
   }
+  ESTAMP_DECL
   const unsigned long long gt0 = ESTAMP_T();
   ESTAMP_ADD(2, 1);
   const bool enc = gjk_enclose(m, o, S, lane, sc);
   const unsigned long long gt1 = ESTAMP_T();
   ESTAMP_ADD(0, gt1 - gt0);
-  if (!enc) return false;
+  if (!enc) {
+    ESTAMP_FLUSH();
+    return false;
+  }
   ESTAMP_ADD(3, 1);
-  const bool hit = epa_penetration(m, o, S, depth, dir, pos, P, lane, grp);
+  const bool hit = epa_penetration(m, o, S, depth, dir, pos, P, lane, grp ESTAMP_ARG);
   ESTAMP_ADD(1, ESTAMP_T() - gt1);
+  ESTAMP_FLUSH();
   return hit;
 }
 
@@ -1054,7 +1191,7 @@ DEV void mpr_obj_setup(const DevModel* __restrict__ m, const EnvShared& sh, int 
   const float4 hc = reinterpret_cast<const float4*>(m->hull_centroid)[k];
   o.hc[0] = hc.x; o.hc[1] = hc.y; o.hc[2] = hc.z;
   o.k = k;
-  o.cells = false;
+  o.sup = kSupScan;
   o.s0 = m->hull_start[k];
   o.n = m->hull_count[k];
 }
@@ -1195,7 +1332,7 @@ DEV bool table_face_snap(const DevModel* __restrict__ m, const EnvShared& sh, in
   const float rc = ax == 0 ? RH[2] : ax == 1 ? RH[5] : RH[8];
   // the hull's extreme vertex along -u: its support in the body-frame direction -sgn (ra, rb, rc) (the first maximal
   // vertex: the cube-map cells' candidates on the fused path, the whole hull on the split path, the same vertex)
-  const float4 v = hull_support(m, o.cells, k, o.s0, o.n, -sgn * ra, -sgn * rb, -sgn * rc, lane);
+  const float4 v = hull_support(m, o.sup, k, o.s0, o.n, -sgn * ra, -sgn * rb, -sgn * rc, lane);
   const float hv[3] = {v.x, v.y, v.z};
   float wb[3];
   mulmv3(wb, RH, hv);
@@ -1424,7 +1561,7 @@ DEV int mpr_contacts(const DevModel* __restrict__ m, const Workspace& w, EnvShar
       p = q < kTableItem0 ? SO100_PAIR_MPR0 + q : SO100_NPAIR_BOX + (q - kTableItem0);
       MprObj o;
       mpr_obj_setup(m, shm[ie], p, o);
-      o.cells = kCells;
+      o.sup = kCells ? kSupFused : kSupScan;
       // Temporal coherence: the direction that proved this pair separated in an earlier substep, re-checked on the
       // current geometry with one support evaluation: max over the Minkowski difference along it below -kSepTol
       // proves the pair separated now, which is GJK's own verdict (it returns no contact for a separated pair and

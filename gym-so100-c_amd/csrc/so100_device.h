@@ -14,7 +14,10 @@ constexpr int kNArm = SO100_NHINGE;
 constexpr int kMaxCon = SO100_MAXCON;     // contacts an env holds on chip (lane c of its row owns contact c)
 constexpr int kConCap = SO100_NCON_MAX;   // the env's whole contact list: every pair at its collider's maximum
 
-constexpr int kCellBlk = 16;   // candidates per support cell block (DevModel::hull_blk): one per lane of a row
+constexpr int kCellBlk = 16;   // candidates per support cell block (the block table, kHullBlkOff): one per lane of a row
+// the vertex index (w, as int bits) of every entry of a block whose cell has no list or a list longer than kCellBlk: the
+// cell takes the list path or the whole-hull scan.  No hull vertex has it, and it is hull_support's "no vertex" too.
+constexpr uint32_t kCellBlkNone = 0x7fffffffu;
 struct DevModel {
   // options
   float timestep;
@@ -89,8 +92,8 @@ struct DevModel {
   // into hull_cand (x, y, z, vertex index bits; count 0: scan the hull)
   uint32_t hull_cells[SO100_NHULL_ALL * SO100_HULL_NCELL];
   const float4_t* hull_cand;
-  // the same lists as fixed blocks of kCellBlk per cell (cell c at c * kCellBlk; lists of <= kCellBlk padded
-  // with their last candidate): a row loads its cell's candidates with one load issued beside the cell entry's
+  // the block table behind this model (kHullBlkOff, below) as a pointer: the 3-wave builds' supports read the cell's
+  // entry, then its block through this pointer (so100_convex.h kSupCells)
   const float4_t* hull_blk;
   float table_top, table_lo[2], table_hi[2];
   float table_bottom;               // the table box's bottom face (table_top - 2 x its half thickness)
@@ -118,6 +121,14 @@ struct DevModel {
   float weld_invw[2];                     // tran, rot
   float mocap0[7];                        // default mocap pose (pos, quat)
 };
+// The support cells' block table lies behind the model in the same device allocation, at this fixed offset: the
+// cells' lists as blocks of kCellBlk candidates (x, y, z, vertex index bits), cell c at kHullBlkOff + c * kHullBlkBytes;
+// a list of 1..kCellBlk candidates padded with its last one, any other cell a block of kCellBlkNone entries.  A row
+// reads its cell's block at the model pointer plus a constant plus cell * 256 + lane * 16: no pointer to fetch first,
+// and the block says itself whether it holds the cell's list, so the support is one memory round.
+constexpr size_t kHullBlkBytes = kCellBlk * sizeof(float4_t);
+constexpr size_t kHullBlkOff = (sizeof(DevModel) + 255u) & ~(size_t)255u;
+constexpr size_t kHullBlkTotal = (size_t)SO100_NHULL_ALL * SO100_HULL_NCELL * kHullBlkBytes;
 
 // ------------------------------------------------------------------ substep workspace (HBM)
 // The substep is split in two kernels: the stage kernel (16 lanes per env) assembles

@@ -1616,12 +1616,17 @@ __global__ void so100_contact_count_kernel(const float* __restrict__ hdr, int n,
 }
 #ifdef SO100_EPA_STAMPS
 }  // namespace so100
+extern "C" int so100_dev_epa_cycles2(unsigned long long* out, int reset);   // the 2-wave build's counters (below)
+// this translation unit's counters plus the 2-wave build's (each keeps its own copy of so100_epa_cyc)
 extern "C" int so100_dev_epa_cycles(unsigned long long* out, int reset) {
+  unsigned long long two[12];
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(so100::so100_epa_cyc), sizeof(unsigned long long) * 12) != hipSuccess) return -1;
   if (reset) {
     unsigned long long z[12] = {};
     if (hipMemcpyToSymbol(HIP_SYMBOL(so100::so100_epa_cyc), z, sizeof(z)) != hipSuccess) return -1;
   }
+  if (so100_dev_epa_cycles2(two, reset) != 0) return -1;
+  for (int k = 0; k < 12; k++) out[k] += two[k];
   return 0;
 }
 namespace so100 {
@@ -1768,6 +1773,18 @@ hipError_t launch_fused2(const DevModel* m, const StageArgs& a, dim3 grid, hipSt
   else hipLaunchKernelGGL((so100_fused_kernel<false, 2, false>), grid, dim3(kThreads), 0, s, m, a);
   return hipGetLastError();
 }
+#ifdef SO100_EPA_STAMPS
+}  // namespace so100
+extern "C" int so100_dev_epa_cycles2(unsigned long long* out, int reset) {
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(so100::so100_epa_cyc), sizeof(unsigned long long) * 12) != hipSuccess) return -1;
+  if (reset) {
+    unsigned long long z[12] = {};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(so100::so100_epa_cyc), z, sizeof(z)) != hipSuccess) return -1;
+  }
+  return 0;
+}
+namespace so100 {
+#endif
 #endif  // SO100_FUSED2_TU
 
 }  // namespace so100

@@ -175,6 +175,8 @@ _lib = None
 ABI_VERSION = 25         # include/so100.h SO100_ABI_VERSION
 HULL_CELLG = 8           # SO100_HULL_CELLG
 HULL_NCELL = 6 * HULL_CELLG * HULL_CELLG
+HULL_BLK = 16            # SO100_HULL_BLK
+HULL_BLK_NONE = 0x7fffffff   # SO100_HULL_BLK_NONE
 
 
 def load():
@@ -237,6 +239,8 @@ def load():
     lib.so100_ee_action.argtypes = [_P, ctypes.POINTER(SO100EeCtrl), _P, _P, _P, _P, _P, _P, _P]
     lib.so100_ee_jacobian.argtypes = [_P, ctypes.c_int, _P, _P, _P, _P]
     lib.so100_hull_cells.argtypes = [_P, _P, _P, ctypes.c_int]
+    lib.so100_hull_blocks.argtypes = [_P, _P, ctypes.c_int]
+    lib.so100_hull_support_probe.argtypes = [_P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P]
     lib.so100_set_fused_build.argtypes = [_P, ctypes.c_int]
     lib.so100_fused_build.argtypes = [_P, ctypes.c_int]
     lib.so100_set_env_packing.argtypes = [_P, ctypes.c_int]
@@ -253,7 +257,8 @@ def load():
                "so100_render_views", "so100_views_sample", "so100_aux_out_bytes", "so100_render_labels",
                "so100_render_aux", "so100_cams_bytes", "so100_render_cams", "so100_shadow_bytes",
                "so100_render_casters", "so100_render_shadow", "so100_msaa_bytes", "so100_render_msaa",
-               "so100_ee_ctrl_bytes", "so100_ee_action", "so100_ee_jacobian"):
+               "so100_ee_ctrl_bytes", "so100_ee_action", "so100_ee_jacobian", "so100_hull_blocks",
+               "so100_hull_support_probe"):
         getattr(lib, fn).restype = ctypes.c_int
     lib.so100_struct_sizes.argtypes = [_P, _P]
     lib.so100_struct_sizes.restype = ctypes.c_int
@@ -298,7 +303,8 @@ EXPORTED_SYMBOLS = ("so100_abi_version", "so100_last_error", "so100_source_hash"
                     "so100_render_views", "so100_views_sample", "so100_aux_out_bytes", "so100_render_labels",
                     "so100_render_aux", "so100_cams_bytes", "so100_render_cams", "so100_shadow_bytes",
                     "so100_render_casters", "so100_render_shadow", "so100_msaa_bytes", "so100_render_msaa",
-                    "so100_ee_ctrl_bytes", "so100_ee_action", "so100_ee_jacobian")
+                    "so100_ee_ctrl_bytes", "so100_ee_action", "so100_ee_jacobian", "so100_hull_blocks",
+                    "so100_hull_support_probe")
 
 
 def source_hash():

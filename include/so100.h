@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SO100_ABI_VERSION 25  /* 25: so100_ee_ctrl / so100_ee_action / so100_ee_jacobian / so100_ee_ctrl_bytes (Cartesian end-effector action mode: a batched damped least-squares prologue in front of so100_step);  24: so100_msaa / so100_render_msaa / so100_msaa_bytes (multisample anti-aliasing, resolved in LDS inside the render launch);  23: so100_shadow / so100_render_shadow / so100_render_casters / so100_shadow_bytes (cast shadows from one light, a shadow map per block);  22: so100_cams / so100_render_cams / so100_cams_bytes (several cameras in one render launch, cameras mounted on a body);  21: so100_render_aux / so100_aux_out / so100_render_labels / so100_aux_out_bytes (depth and segmentation images from the render launch);  20: so100_view / so100_render_views / so100_render_materials / so100_views_sample / so100_view_bytes (camera, lights and colours per env);  19: so100_render_to / so100_image_out (one render launch, several sinks: hwc, chw, flat float32);  18: env packing of the fused step (so100_set_env_packing, so100_env_packing, so100_env_order, so100_env_cost, so100_wave_cost);  17: so100_pool_stats (the fused step's contact-record pool, sized never to run out);  16: so100_source_hash;  15: the EE variant's mocap marker box collides (SO100_NGEOM 16, SO100_NPAIR 209, SO100_NCON_MAX 643, debug stride 3,922);  14: no per-env contact cap (SO100_NCON_MAX: every pair at its collider's maximum), debug stride 3,436 (SO100_DBG_OVF), ncon_dropped always 0, status -3 for a caught C++ exception;  13: so100_buffers.ep_return / ep_final / ep_accum (device-side episode statistics);  12: so100_model.convex (GJK/EPA mesh collider, MuJoCo 3.3.3 default), box-box up to 8 contacts, cube-table one convex contact;  11: so100_buffers.ncon_dropped, debug stride 160 (contact friction forces), so100_set_fused_build;  10: so100_hull_cells (MPR support lookup);  9: pad/link-hull pairs (SO100_NPAIR 191);  8: fused step kernel, so100_set_step_mode;  7: reward64 buffer;  6: Base hull + pad pairs (SO100_NPAIR 155, SO100_NHULL_ALL 10); 5: EE/mocap weld, render API */
+#define SO100_ABI_VERSION 25  /* (added without a new version, no existing entry point or struct changes: so100_hull_blocks / so100_hull_support_probe, the support cells' self-describing block table behind the device model and the step kernels' hull support on its own; a caller finds them by symbol);  25: so100_ee_ctrl / so100_ee_action / so100_ee_jacobian / so100_ee_ctrl_bytes (Cartesian end-effector action mode: a batched damped least-squares prologue in front of so100_step);  24: so100_msaa / so100_render_msaa / so100_msaa_bytes (multisample anti-aliasing, resolved in LDS inside the render launch);  23: so100_shadow / so100_render_shadow / so100_render_casters / so100_shadow_bytes (cast shadows from one light, a shadow map per block);  22: so100_cams / so100_render_cams / so100_cams_bytes (several cameras in one render launch, cameras mounted on a body);  21: so100_render_aux / so100_aux_out / so100_render_labels / so100_aux_out_bytes (depth and segmentation images from the render launch);  20: so100_view / so100_render_views / so100_render_materials / so100_views_sample / so100_view_bytes (camera, lights and colours per env);  19: so100_render_to / so100_image_out (one render launch, several sinks: hwc, chw, flat float32);  18: env packing of the fused step (so100_set_env_packing, so100_env_packing, so100_env_order, so100_env_cost, so100_wave_cost);  17: so100_pool_stats (the fused step's contact-record pool, sized never to run out);  16: so100_source_hash;  15: the EE variant's mocap marker box collides (SO100_NGEOM 16, SO100_NPAIR 209, SO100_NCON_MAX 643, debug stride 3,922);  14: no per-env contact cap (SO100_NCON_MAX: every pair at its collider's maximum), debug stride 3,436 (SO100_DBG_OVF), ncon_dropped always 0, status -3 for a caught C++ exception;  13: so100_buffers.ep_return / ep_final / ep_accum (device-side episode statistics);  12: so100_model.convex (GJK/EPA mesh collider, MuJoCo 3.3.3 default), box-box up to 8 contacts, cube-table one convex contact;  11: so100_buffers.ncon_dropped, debug stride 160 (contact friction forces), so100_set_fused_build;  10: so100_hull_cells (MPR support lookup);  9: pad/link-hull pairs (SO100_NPAIR 191);  8: fused step kernel, so100_set_step_mode;  7: reward64 buffer;  6: Base hull + pad pairs (SO100_NPAIR 155, SO100_NHULL_ALL 10); 5: EE/mocap weld, render API */
 
 /* tasks (gym_so100/__init__.py:4-32 ids; single_arm.py task classes) */
 #define SO100_TASK_CUBE_TO_BIN 0          /* gym_so100/SO100CubeToBin-v0, TimeLimit 700 */
@@ -173,6 +173,25 @@ int so100_fused_build(const so100_env* env, int debug);
  * Returns the number of candidates (cand may be NULL to query it), -1 on error. */
 /* (SO100_HULL_CELLG, SO100_HULL_NCELL: so100_model.h) */
 int so100_hull_cells(const so100_model* model, uint32_t* cells, float* cand, int cap);
+
+/* The cells' block table, exactly as so100_create uploads it behind the device model (host only; added under ABI 25): the fused
+ * step's 2-wave build reads one block per support and nothing else (its 3-wave builds read the cell's entry first).  SO100_HULL_BLK = 16 entries (x, y, z, vertex
+ * index as float bits) per cell, cell c at blk[16 c .. 16 c + 15]: a cell whose list has 1..16 candidates holds the
+ * list, padded with its last candidate; a cell with no list or a longer one holds 16 entries of zero coordinates and
+ * the index SO100_HULL_BLK_NONE, and the kernel goes on to the cell's entry (so100_hull_cells).
+ *   blk[cap][4]; returns the number of entries (SO100_NHULL_ALL * SO100_HULL_NCELL * 16; blk may be NULL to query
+ * it), -1 on error. */
+#define SO100_HULL_BLK 16
+#define SO100_HULL_BLK_NONE 0x7fffffff
+int so100_hull_blocks(const so100_model* model, float* blk, int cap);
+
+/* The step kernels' hull support on its own (a test probe; added under ABI 25): for each of the n directions dirs[n][3] (DEVICE
+ * float32) the first vertex of hull `hull` (0 .. SO100_NHULL_ALL - 1) maximising dir . v: use_cells 1 through the cells'
+ * block table alone (the fused step's 2-wave build: one load per support), 2 through the cell's entry and then its
+ * block (the fused step's 3-wave builds), 0 by the whole-hull scan (the split step): out[n][4] (DEVICE) takes the
+ * vertex (x, y, z) and its index within the hull (as float bits).  One workgroup per 16 directions on the null
+ * stream; returns after the kernel has finished.  0, or -1 on error. */
+int so100_hull_support_probe(so100_env* env, int hull, const float* dirs, int n, int use_cells, float* out);
 
 /* Number of env chunks and the env count of chunk 0 (the launches so100_profile_read times). */
 int so100_chunk_info(const so100_env* env, int* nchunks, int* profiled_envs);

@@ -1,7 +1,9 @@
 """Convex-collider phase cycles on the GPU (dev probe; needs the -DSO100_EPA_STAMPS library variant):
     SO100_LIB=.../libso100_hip_epastamps.so python tools/dev/epa_stamps.py [n] [fused]
 Steps n bench envs 60 steps, then sums over 5 steps per row-item: GJK and EPA cycles, EPA iterations, and
-inside EPA the nearest-facet scan, the support and the horizon + new facets."""
+inside EPA the nearest-facet scan, the support and the horizon + new facets.  so100_dev_epa_cycles sums the counters
+of both translation units of the step kernels (the 3-wave builds' and the 2-wave build's, which 8,192 envs run); an
+item's deltas are added once, when the item ends, so no atomic sits between two stamps."""
 import ctypes
 import os
 import sys
