@@ -60,6 +60,10 @@ hipError_t launch_ee_action(const DevModel*, const so100_ee_ctrl&, int, const fl
                             float*, float*, float*, hipStream_t);
 hipError_t launch_ee_jacobian(const DevModel*, int, const float*, float*, float*, hipStream_t);
 hipError_t launch_hull_support_probe(const DevModel*, int, const float*, int, int, float*, hipStream_t);
+hipError_t launch_dr_sample(const so100_dr_ranges&, const uint32_t*, const uint8_t*, const uint8_t*, float*, float*, int,
+                            int, hipStream_t);
+hipError_t launch_actuate(const DevModel*, int, const float*, const float*, const uint8_t*, const float*, float*,
+                          int32_t*, float*, hipStream_t);
 }  // namespace so100
 
 using so100::DevModel;
@@ -1600,6 +1604,39 @@ static int so100_ee_jacobian_impl(so100_env* env, int n, const float* qpos, floa
   return e == hipSuccess ? 0 : fail_hip("so100_ee_jacobian", e);
 }
 
+static int so100_dr_sample_impl(so100_env* env, const so100_dr_ranges* r, const uint32_t* episode, const uint8_t* mask_a,
+                                const uint8_t* mask_b, float* dr_params, float* act_params, void* stream) {
+  if (!r) return fail("so100_dr_sample: NULL ranges");
+  if (r->size != sizeof(so100_dr_ranges))
+    return size_mismatch("so100_dr_sample", "so100_dr_ranges", r->size, sizeof(so100_dr_ranges));
+  if (!env) return fail("so100_dr_sample: NULL env");
+  if (!dr_params && !act_params) return fail("so100_dr_sample: NULL dr_params and act_params (nothing to draw)");
+  auto positive = [](const float* p) { return std::isfinite(p[0]) && std::isfinite(p[1]) && p[0] > 0.f && p[0] <= p[1]; };
+  if (!positive(r->mass)) return fail("so100_dr_sample: mass range must be finite with 0 < lo <= hi");
+  if (!positive(r->friction)) return fail("so100_dr_sample: friction range must be finite with 0 < lo <= hi");
+  if (r->delay[0] < 0 || r->delay[1] > SO100_ACT_MAX_DELAY || r->delay[0] > r->delay[1])
+    return fail("so100_dr_sample: delay range must lie in 0..7 with lo <= hi");
+  if (!(r->smoothing[0] > 0.f && r->smoothing[1] <= 1.f && r->smoothing[0] <= r->smoothing[1]))     // false for NaN
+    return fail("so100_dr_sample: smoothing range must lie in (0, 1] with lo <= hi");
+  if (!positive(r->rate)) return fail("so100_dr_sample: rate range must be finite with 0 < lo <= hi");
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_dr_sample(*r, episode, mask_a, mask_b, dr_params, act_params, env->n, env->env_offset,
+                                         (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip("so100_dr_sample", e);
+}
+
+static int so100_actuate_impl(so100_env* env, const float* qpos, const float* command, const uint8_t* reinit,
+                              const float* act_params, float* hist, int32_t* head, float* action, void* stream) {
+  if (!env) return fail("so100_actuate: NULL env");
+  if (!qpos || !command || !act_params || !hist || !head || !action)
+    return fail("so100_actuate: NULL qpos, command, act_params, hist, head or action");
+  if (env->ee) return fail("so100_actuate: the model has ee = 1 (the weld variant takes a mocap pose, not an action)");
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_actuate(env->d_model, env->n, qpos, command, reinit, act_params, hist, head, action,
+                                       (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip("so100_actuate", e);
+}
+
 // the step kernels' hull support for n directions of one hull (device buffers; the null stream, waited for)
 static int so100_hull_support_probe_impl(so100_env* env, int hull, const float* dirs, int n, int use_cells, float* out) {
   if (!env || !dirs || !out || n < 0) return fail("so100_hull_support_probe: bad arguments");
@@ -1630,6 +1667,26 @@ int so100_hull_support_probe(so100_env* env, int hull, const float* dirs, int n,
   }
 }
 
+
+int so100_dr_ranges_bytes(void) { return (int)sizeof(so100_dr_ranges); }
+
+int so100_dr_sample(so100_env* env, const so100_dr_ranges* ranges, const uint32_t* episode, const uint8_t* mask_a,
+                    const uint8_t* mask_b, float* dr_params, float* act_params, void* stream) {
+  try {
+    return so100_dr_sample_impl(env, ranges, episode, mask_a, mask_b, dr_params, act_params, stream);
+  } catch (...) {
+    return caught("so100_dr_sample");
+  }
+}
+
+int so100_actuate(so100_env* env, const float* qpos, const float* command, const uint8_t* reinit,
+                  const float* act_params, float* hist, int32_t* head, float* action, void* stream) {
+  try {
+    return so100_actuate_impl(env, qpos, command, reinit, act_params, hist, head, action, stream);
+  } catch (...) {
+    return caught("so100_actuate");
+  }
+}
 
 int so100_ee_ctrl_bytes(void) { return (int)sizeof(so100_ee_ctrl); }
 

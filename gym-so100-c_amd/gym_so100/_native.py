@@ -131,6 +131,30 @@ class SO100EeCtrl(ctypes.Structure):
         self.ws_hi[:] = [float(x) for x in ws_hi]
 
 
+SO100_ACT_MAX_DELAY = 7            # include/so100.h: the longest actuation delay, control steps
+SO100_ACT_HIST = 8                 # the command ring's slots
+
+
+class SO100DrRanges(ctypes.Structure):
+    """Mirror of ``so100_dr_ranges`` (include/so100.h): the ranges one ``so100_dr_sample`` launch draws the physical
+    randomisation and the actuator records from.  The default is every range at zero width and off (scales 1, no delay,
+    no smoothing, no slew limit); ``size`` is set to the mirror's size, which the callee checks against its own."""
+    _fields_ = [("size", ctypes.c_uint32), ("reserved0", ctypes.c_uint32), ("seed", ctypes.c_uint64),
+                ("mass", ctypes.c_float * 2), ("friction", ctypes.c_float * 2), ("delay", ctypes.c_int32 * 2),
+                ("smoothing", ctypes.c_float * 2), ("rate", ctypes.c_float * 2)]
+
+    def __init__(self, seed=0, mass=(1.0, 1.0), friction=(1.0, 1.0), delay=(0, 0), smoothing=(1.0, 1.0),
+                 rate=(2.0, 2.0)):
+        super().__init__()
+        self.size = ctypes.sizeof(SO100DrRanges)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.mass[:] = [float(x) for x in mass]
+        self.friction[:] = [float(x) for x in friction]
+        self.delay[:] = [int(x) for x in delay]
+        self.smoothing[:] = [float(x) for x in smoothing]
+        self.rate[:] = [float(x) for x in rate]
+
+
 SO100_NMATERIAL = 5
 
 
@@ -238,6 +262,9 @@ def load():
     lib.so100_ee_ctrl_bytes.argtypes = []
     lib.so100_ee_action.argtypes = [_P, ctypes.POINTER(SO100EeCtrl), _P, _P, _P, _P, _P, _P, _P]
     lib.so100_ee_jacobian.argtypes = [_P, ctypes.c_int, _P, _P, _P, _P]
+    lib.so100_dr_ranges_bytes.argtypes = []
+    lib.so100_dr_sample.argtypes = [_P, ctypes.POINTER(SO100DrRanges), _P, _P, _P, _P, _P, _P]
+    lib.so100_actuate.argtypes = [_P, _P, _P, _P, _P, _P, _P, _P, _P]
     lib.so100_hull_cells.argtypes = [_P, _P, _P, ctypes.c_int]
     lib.so100_hull_blocks.argtypes = [_P, _P, ctypes.c_int]
     lib.so100_hull_support_probe.argtypes = [_P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P]
@@ -258,7 +285,7 @@ def load():
                "so100_render_aux", "so100_cams_bytes", "so100_render_cams", "so100_shadow_bytes",
                "so100_render_casters", "so100_render_shadow", "so100_msaa_bytes", "so100_render_msaa",
                "so100_ee_ctrl_bytes", "so100_ee_action", "so100_ee_jacobian", "so100_hull_blocks",
-               "so100_hull_support_probe"):
+               "so100_hull_support_probe", "so100_dr_ranges_bytes", "so100_dr_sample", "so100_actuate"):
         getattr(lib, fn).restype = ctypes.c_int
     lib.so100_struct_sizes.argtypes = [_P, _P]
     lib.so100_struct_sizes.restype = ctypes.c_int
@@ -288,6 +315,9 @@ def load():
     if lib.so100_ee_ctrl_bytes() != ctypes.sizeof(SO100EeCtrl):
         raise NativeLibraryError(f"struct layout mismatch: so100_ee_ctrl {lib.so100_ee_ctrl_bytes()} vs "
                                  f"{ctypes.sizeof(SO100EeCtrl)}")
+    if lib.so100_dr_ranges_bytes() != ctypes.sizeof(SO100DrRanges):
+        raise NativeLibraryError(f"struct layout mismatch: so100_dr_ranges {lib.so100_dr_ranges_bytes()} vs "
+                                 f"{ctypes.sizeof(SO100DrRanges)}")
     _lib = lib
     return lib
 
@@ -304,7 +334,7 @@ EXPORTED_SYMBOLS = ("so100_abi_version", "so100_last_error", "so100_source_hash"
                     "so100_render_aux", "so100_cams_bytes", "so100_render_cams", "so100_shadow_bytes",
                     "so100_render_casters", "so100_render_shadow", "so100_msaa_bytes", "so100_render_msaa",
                     "so100_ee_ctrl_bytes", "so100_ee_action", "so100_ee_jacobian", "so100_hull_blocks",
-                    "so100_hull_support_probe")
+                    "so100_hull_support_probe", "so100_dr_ranges_bytes", "so100_dr_sample", "so100_actuate")
 
 
 def source_hash():

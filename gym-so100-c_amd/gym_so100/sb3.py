@@ -40,6 +40,10 @@ resolved inside the render launch, with no further host copy.
 ``action_mode="ee_delta"`` (and ``ee_control``) is forwarded to the env: the action space is then ``Box(-1, 1, (5,))``,
 the Cartesian delta (dx, dy, dz, droll, grip) a device prologue turns into the joint actions of the unchanged step.
 
+``domain_randomization`` is handed to the env as it is, its ``per_episode`` and ``actuation`` keys included (physical
+parameters drawn again for every new episode; a per-env actuation delay, smoothing and slew limit between the action and
+the step): both run on the device, and the adapter's contract does not change.
+
 The image (or flattened) tensor reaches the host by one asynchronous copy into pinned memory and one stream
 synchronisation per step.  Two pinned buffers alternate: **the image array of an observation returned by
 ``reset()`` / ``step()`` stays valid through the next ``step()`` and is overwritten by the one after it** (SB3's

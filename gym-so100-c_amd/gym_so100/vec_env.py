@@ -105,6 +105,61 @@ def ee_control_options(control, model=None):
     return c
 
 
+# the actuation model's ranges with the model off (include/so100.h so100_dr_ranges): no delay, alpha = 1, no slew limit
+ACTUATION_OFF = {"delay": (0, 0), "smoothing": (1.0, 1.0), "rate": (2.0, 2.0)}
+ACT_MAX_DELAY = 7                  # SO100_ACT_MAX_DELAY
+
+
+def _real_range(what, value, upper=None):
+    """(lo, hi) floats of a range argument; ValueError for what so100_dr_sample refuses"""
+    try:
+        lo, hi = (float(x) for x in value)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: {value!r} is not a (lo, hi) pair of numbers") from None
+    if not (np.isfinite(lo) and np.isfinite(hi)) or lo <= 0 or lo > hi or (upper is not None and hi > upper):
+        raise ValueError(f"{what}: {value!r} must be finite with 0 < lo <= hi" + ("" if upper is None else f" <= {upper}"))
+    return lo, hi
+
+
+def actuation_options(actuation):
+    """The checked ranges of domain_randomization["actuation"] as a dict (no device use): ACTUATION_OFF overridden by
+    `actuation`.  Raises ValueError for unknown keys and for what so100_dr_sample refuses."""
+    if not isinstance(actuation, dict):
+        raise ValueError("actuation: a dict(delay=(lo, hi), smoothing=(lo, hi), rate=(lo, hi))")
+    unknown = set(actuation) - set(ACTUATION_OFF)
+    if unknown:
+        raise ValueError(f"actuation: unknown keys {sorted(unknown)}; known: {sorted(ACTUATION_OFF)}")
+    a = dict(ACTUATION_OFF)
+    a.update(actuation)
+    try:
+        lo, hi = a["delay"]
+    except (TypeError, ValueError):
+        raise ValueError(f"actuation: delay {a['delay']!r} is not a (lo, hi) pair") from None
+    for v in (lo, hi):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"actuation: delay {a['delay']!r} must be whole control steps")
+    if lo < 0 or hi > ACT_MAX_DELAY or lo > hi:
+        raise ValueError(f"actuation: delay {a['delay']!r} must lie in 0..{ACT_MAX_DELAY} with lo <= hi")
+    return {"delay": (int(lo), int(hi)), "smoothing": _real_range("actuation: smoothing", a["smoothing"], upper=1.0),
+            "rate": _real_range("actuation: rate", a["rate"])}
+
+
+def physical_dr_options(dr, variant="joint"):
+    """The argument checks of a domain_randomization dict's per_episode / actuation keys (no device use): ValueError for
+    what so100_dr_sample would refuse and for an actuation model on variant="ee".  The other keys are checked as they
+    always were."""
+    if not dr:
+        return
+    if dr.get("actuation") is not None:
+        if variant == "ee":
+            raise ValueError("domain_randomization['actuation'] models the joint command's latency; variant='ee' takes "
+                             "its mocap pose (set_mocap)")
+        actuation_options(dr["actuation"])
+    if dr.get("per_episode"):
+        _real_range("domain_randomization: mass", dr.get("mass", (0.8, 1.2)))
+        _real_range("domain_randomization: friction", dr.get("friction", (0.8, 1.2)))
+
+
 class SO100VecEnv:
     """N parallel SO-ARM100 envs on one GPU.
 
@@ -124,7 +179,14 @@ class SO100VecEnv:
         domain_randomization: None or dict(mass=(lo,hi), friction=(lo,hi), action_noise=sigma):
             per-env cube mass / friction scales (fixed per env) + Gaussian action noise.  With pixel observations
             the dict may carry ``visual=dict(...)``: camera jitter, light and colour randomisation per env
-            (``set_domain_randomization``); ValueError with any other obs_type.
+            (``set_domain_randomization``); ValueError with any other obs_type.  Two more keys, both off by default:
+            ``per_episode=True`` draws mass and friction on the device (csrc/so100_dr.hip) from each env's episode
+            counter, again whenever an env is reset, by ``reset`` or by auto-reset, with no host synchronisation;
+            ``actuation=dict(delay=(lo,hi), smoothing=(lo,hi), rate=(lo,hi))`` puts an actuator model between the
+            command and the step (csrc/so100_act.hip, include/so100.h so100_actuate): per env a delay of whole control
+            steps (0..7), a first-order smoothing factor and a slew limit per control step, drawn per env (per episode
+            with ``per_episode``) into ``act_params`` [N,4]; ``actions`` then holds the applied action, and an
+            ``action_mode="ee_delta"`` command passes EE prologue -> actuator -> step.  ValueError with variant="ee".
         env_offset: global index of this shard's first env (multi-GPU sharding); in-kernel seeds use
             the global env id so trajectories do not depend on the number of GPUs.
         iterations: solver iterations per substep, PGS sweeps or Newton steps (default: the model's 100,
@@ -240,6 +302,7 @@ class SO100VecEnv:
             cameras = check_camera_names(cameras)
             if not all(isinstance(c, str) for c in cameras):
                 raise ValueError("cameras: a tuple of camera names")
+        physical_dr_options(domain_randomization, variant)       # its ValueErrors before any device work
         if domain_randomization and domain_randomization.get("visual") is not None:
             if obs_type != "so100_pixels_agent_pos":
                 raise ValueError("domain_randomization['visual'] needs obs_type='so100_pixels_agent_pos'")
@@ -276,6 +339,10 @@ class SO100VecEnv:
         self.action_dim = 6
         self.ee_actions = self.ee_joint_target = self.ee_target = self.reinit = None
         self.ee_control = self._ee_ctrl = None
+        self.act_params = self.act_hist = self.act_head = self.act_command = None
+        self._act = False               # the actuation model is on (set_domain_randomization(actuation=...))
+        self._dr_ranges = None          # the record so100_dr_sample draws from, while something is drawn on the device
+        self._dr_per_episode = False
         if action_mode == "ee_delta":
             self.action_dim = 5
             self.ee_control = ee_control_options(ee_control, self.model)
@@ -286,6 +353,8 @@ class SO100VecEnv:
             self.reinit = torch.ones(n, dtype=torch.uint8, device=d)        # every command starts from its env's pose
             self._reinit_bool = self.reinit.view(torch.bool)
             self._reinit_pending = True                                      # host side: some byte of reinit may be set
+        self._routed = self._ee_ctrl is not None       # a prologue writes ``actions``: the step never reads an action buffer
+        self._pre = self._routed                       # a step is more than the so100_step launch
         self.obs = torch.zeros(n, NOBS, dtype=f32, device=d)
         self.reward = torch.zeros(n, dtype=f32, device=d)
         self.terminated = torch.zeros(n, dtype=torch.bool, device=d)
@@ -359,8 +428,9 @@ class SO100VecEnv:
             setattr(b, name, P(getattr(self, name)))
         if not getattr(self, "_debug_enabled", True):
             b.debug = None
-        # (ee_delta: the step always reads the joint actions the prologue writes; an action buffer feeds the prologue)
-        b.action = P(self.actions) if getattr(self, "_action_ref", None) is None or self._ee_ctrl is not None \
+        # (ee_delta, actuation: the step always reads the joint actions the prologue writes; an action buffer feeds the
+        # prologue)
+        b.action = P(self.actions) if getattr(self, "_action_ref", None) is None or self._routed \
             else P(self._action_ref)
 
     def set_mocap(self, pos, quat=None, mask=None):
@@ -399,7 +469,8 @@ class SO100VecEnv:
         ranges, per_episode, seed = self._visual
         self.renderer.sample_views(ranges, seed, episode=self.episode if per_episode else None, mask=mask)
 
-    def set_domain_randomization(self, mass=(0.8, 1.2), friction=(0.8, 1.2), action_noise=0.05, seed=None, visual=None):
+    def set_domain_randomization(self, mass=(0.8, 1.2), friction=(0.8, 1.2), action_noise=0.05, seed=None, visual=None,
+                                 per_episode=False, actuation=None):
         """Per-env cube mass scale, contact friction scale (fixed per env) and action-noise sigma.
 
         The scales are a counter-based hash of (seed, global env id), so an env draws the same parameters
@@ -412,13 +483,30 @@ class SO100VecEnv:
         light direction), colors (one (lo, hi) per-channel scale or a dict by render.MATERIALS name), per_episode
         (default False: drawn once; True: an env's view is drawn again from its episode counter whenever it is reset,
         the terminal image in final_pixels still showing the finished episode's view) and seed (default: the env's
-        base seed).  It touches images only; the physical part above applies as without it."""
+        base seed).  It touches images only; the physical part above applies as without it.
+
+        per_episode (default False: ``dr_params`` is the host draw above and is never rewritten): True draws mass and
+        friction on the device instead (so100_dr_sample: the visual part's hash of (seed, global env id, episode, field),
+        fields 1 and 2), from each env's episode counter: now, after every ``reset`` for the reset envs and, with
+        auto-reset, after every step for the envs that finished, on the caller's stream with no host synchronisation.
+        ``dr_params`` keeps its address.
+
+        actuation (default None: the command is the applied action): a dict of up to three ranges, delay=(lo, hi) whole
+        control steps in 0..7, smoothing=(lo, hi) in (0, 1], rate=(lo, hi) > 0 in normalised action units per control
+        step; a missing key is off (ACTUATION_OFF).  Each env draws (delay, alpha, rate) into ``act_params`` [N,4] (fields
+        4, 5, 6; once, or per episode with per_episode), and every step so100_actuate turns the clipped command into the
+        applied action in ``actions``: the command of `delay` steps earlier, smoothed by y + alpha (v - y), moved by at
+        most `rate`.  After a reset the actuator holds the measured pose until the first delayed command arrives
+        (``reinit``).  The step's action noise is added after it.  ValueError with variant="ee" and for out-of-range
+        values."""
         torch = _torch()
+        physical_dr_options({"mass": mass, "friction": friction, "per_episode": per_episode, "actuation": actuation},
+                            self.variant)
         if visual is not None:
             if self.obs_type != "so100_pixels_agent_pos":
                 raise ValueError("domain_randomization['visual'] needs obs_type='so100_pixels_agent_pos'")
-            ranges, per_episode, vseed = self._check_visual(visual)
-            self._visual = (ranges, per_episode, self.base_seed if vseed is None else int(vseed))
+            ranges, view_per_episode, vseed = self._check_visual(visual)
+            self._visual = (ranges, view_per_episode, self.base_seed if vseed is None else int(vseed))
         else:
             self._visual = None
         if getattr(self, "renderer", None) is not None:      # (the constructor samples once its renderer exists)
@@ -432,10 +520,47 @@ class SO100VecEnv:
         p[:, 0] = torch.from_numpy(mass[0] + (mass[1] - mass[0]) * _hash_uniform(s, ids, 1))
         p[:, 1] = torch.from_numpy(friction[0] + (friction[1] - friction[0]) * _hash_uniform(s, ids, 2))
         p[:, 2] = float(action_noise)
+        self._dr_per_episode = bool(per_episode)
+        self._act = actuation is not None
+        self._dr_ranges = None
+        if self._dr_per_episode:
+            p[:, :2] = 0.0                          # drawn on the device below
         self.dr_params = p.to(self.device)
+        if self._dr_per_episode or self._act:
+            act = actuation_options(actuation) if self._act else ACTUATION_OFF
+            self._dr_ranges = _native.SO100DrRanges(seed=s, mass=mass if self._dr_per_episode else (1.0, 1.0),
+                                                    friction=friction if self._dr_per_episode else (1.0, 1.0), **act)
+        n, d = self.num_envs, self.device
+        if self._act:
+            if self.act_params is None:
+                self.act_params = torch.zeros(n, 4, dtype=torch.float32, device=d)
+                self.act_hist = torch.zeros(_native.SO100_ACT_HIST, n, 6, dtype=torch.float32, device=d)
+                self.act_head = torch.zeros(n, dtype=torch.int32, device=d)
+                self.act_command = torch.zeros(n, 6, dtype=torch.float32, device=d)   # the command step() copies into
+            if self.reinit is None:                  # (ee_delta has it already: the two prologues share it)
+                self.reinit = torch.ones(n, dtype=torch.uint8, device=d)
+                self._reinit_bool = self.reinit.view(torch.bool)
+            self.reinit.fill_(1)                     # every actuator starts from its env's pose
+            self._reinit_pending = True
+        self._routed = self._ee_ctrl is not None or self._act
+        self._pre = self._routed or self._dr_per_episode
+        if self._dr_ranges is not None:
+            self._dr_sample(None, None, act_only=not self._dr_per_episode)
         self._flags |= _native.SO100_FLAG_DR
         if hasattr(self, "_buf"):
             self._fill_buffers()
+
+    def _dr_sample(self, mask_a, mask_b, act_only=False, keep_act=False):
+        """so100_dr_sample on the current stream: the dr_params rows (unless act_only) and, with the actuation model
+        (unless keep_act), the act_params rows of the envs in either byte mask (None, None: every env), per_episode: from
+        the episode counter"""
+        P = _native.ptr
+        _native.check(self.lib.so100_dr_sample(self._handle, ctypes.byref(self._dr_ranges),
+                                               P(self.episode) if self._dr_per_episode else None, P(mask_a), P(mask_b),
+                                               None if act_only else P(self.dr_params),
+                                               P(self.act_params) if self._act and not keep_act else None,
+                                               self._stream()),
+                      "so100_dr_sample")
 
     # ------------------------------------------------------------------ API
     def reset(self, seed=None, mask=None):
@@ -463,7 +588,9 @@ class SO100VecEnv:
             mask_p = _native.ptr(self._mask)
         _native.check(self.lib.so100_reset(self._handle, ctypes.byref(self._buf), mask_p, seeds_p, self._stream()),
                       "so100_reset")
-        if self._ee_ctrl is not None:                    # the reset envs' commands start again from their fresh pose
+        if self._dr_per_episode:                         # the reset envs' new episodes: their physical parameters
+            self._dr_sample(None if mask is None else self._mask, None)
+        if self._routed:                                 # the reset envs' commands start again from their fresh pose
             if mask is None:
                 self.reinit.fill_(1)
             else:
@@ -483,7 +610,7 @@ class SO100VecEnv:
             self._action_ref = None
             self._buf.action = _native.ptr(self.actions)
         k = self.action_dim
-        dst = self.actions if self._ee_ctrl is None else self.ee_actions
+        dst = self.ee_actions if self._ee_ctrl is not None else (self.act_command if self._act else self.actions)
         if isinstance(actions, torch.Tensor):
             if actions.shape != (self.num_envs, k):
                 raise ValueError(f"actions must be [{self.num_envs}, {k}], got {tuple(actions.shape)}")
@@ -497,16 +624,18 @@ class SO100VecEnv:
             if a.shape != (self.num_envs, k):
                 raise ValueError(f"actions must be [{self.num_envs}, {k}], got {a.shape}")
             dst.copy_(torch.from_numpy(a))
-        if self._ee_ctrl is not None:
-            self._ee_prologue()
+        if self._routed:
+            self._prologue()
         if self.renderer is None:
             _native.check(self.lib.so100_step(self._handle, ctypes.byref(self._buf), self._flags, self._stream()),
                           "so100_step")
             done = self.terminated | self.truncated
+            if self._dr_per_episode and self.autoreset:  # the step has bumped the finished envs' episode counters
+                self._dr_sample(self.terminated, self.truncated)
         else:
             done = self._step_pixels()
-        if self._ee_ctrl is not None:
-            self._ee_epilogue()
+        if self._routed:
+            self._epilogue()
         info = {"is_success": self.success, "diverged": self.diverged, "contact_bits": self.contact_bits,
                 "ncon_dropped": self.ncon_dropped}
         if self.autoreset:
@@ -524,27 +653,39 @@ class SO100VecEnv:
     def set_action_buffer(self, actions):
         """Point the kernel's action input at a resident [N,6] float32 device tensor (zero copy).
         The tensor must stay alive until the next call; ``step()`` copies into ``self.actions``.
-        action_mode="ee_delta": a [N,5] tensor, read by the prologue that fills ``self.actions``."""
+        action_mode="ee_delta": a [N,5] tensor, read by the prologue that fills ``self.actions``; with the actuation
+        model the tensor is the command the actuator reads."""
         torch = _torch()
         k = self.action_dim
         if actions.shape != (self.num_envs, k) or actions.dtype != torch.float32 or not actions.is_contiguous() \
                 or actions.device != self.device:
             raise ValueError(f"action buffer must be a contiguous float32 [N,{k}] tensor on the env's device")
         self._action_ref = actions
-        if self._ee_ctrl is None:
+        if not self._routed:
             self._buf.action = _native.ptr(actions)
 
-    def _ee_prologue(self):
-        """ee_delta: the delta actions (``ee_actions`` or the action buffer) -> ``actions``, on the current stream"""
-        src = self.ee_actions if getattr(self, "_action_ref", None) is None else self._action_ref
+    def _prologue(self):
+        """ee_delta and / or the actuation model, on the current stream: the delta actions (``ee_actions`` or the action
+        buffer) -> joint command -> ``actions``; the joint command is ``act_command`` (or the action buffer) when the
+        actuator follows, else ``actions`` itself"""
+        ref = getattr(self, "_action_ref", None)
         P = _native.ptr
-        _native.check(self.lib.so100_ee_action(self._handle, ctypes.byref(self._ee_ctrl), P(self.qpos), P(src),
-                                               P(self.reinit), P(self.ee_joint_target), P(self.actions),
-                                               P(self.ee_target), self._stream()), "so100_ee_action")
+        if self._ee_ctrl is not None:
+            src = self.ee_actions if ref is None else ref
+            _native.check(self.lib.so100_ee_action(self._handle, ctypes.byref(self._ee_ctrl), P(self.qpos), P(src),
+                                                   P(self.reinit), P(self.ee_joint_target),
+                                                   P(self.act_command if self._act else self.actions),
+                                                   P(self.ee_target), self._stream()), "so100_ee_action")
+            ref = None
+        if self._act:
+            src = self.act_command if ref is None else ref
+            _native.check(self.lib.so100_actuate(self._handle, P(self.qpos), P(src), P(self.reinit), P(self.act_params),
+                                                 P(self.act_hist), P(self.act_head), P(self.actions), self._stream()),
+                          "so100_actuate")
 
-    def _ee_epilogue(self):
-        """ee_delta: after the step, mark the envs whose command starts from their pose at the next step: with
-        auto-reset the envs that just finished (their qpos is a new episode's), else none"""
+    def _epilogue(self):
+        """ee_delta / actuation: after the step, mark the envs whose command starts from their pose at the next step:
+        with auto-reset the envs that just finished (their qpos is a new episode's), else none"""
         if self.autoreset:
             _torch().logical_or(self.terminated, self.truncated, out=self._reinit_bool)
         elif self._reinit_pending:
@@ -568,6 +709,8 @@ class SO100VecEnv:
                                                s), "so100_reset")
             if self._visual is not None and self._visual[1]:
                 self._sample_views(self._mask)         # the new episodes' views: final_pixels is already drawn
+            if self._dr_per_episode:
+                self._dr_sample(self._mask, None)      # and their physical parameters
         self._render_all()
         return done
 
@@ -602,11 +745,16 @@ class SO100VecEnv:
     def step_async_raw(self):
         """Launch one env step on the current stream using the actions already in ``self.actions``
         (no argument handling, no output views) — the benchmark's hot loop.  action_mode="ee_delta": the delta
-        actions already in ``self.ee_actions`` (or the action buffer), through the prologue."""
-        if self._ee_ctrl is not None:
-            self._ee_prologue()
+        actions already in ``self.ee_actions`` (or the action buffer), through the prologue; with the actuation model
+        the command already in ``self.act_command`` (or the action buffer)."""
+        if self._pre:
+            if self._routed:
+                self._prologue()
             self.lib.so100_step(self._handle, ctypes.byref(self._buf), self._flags, self._stream())
-            self._ee_epilogue()
+            if self._dr_per_episode and self.autoreset:
+                self._dr_sample(self.terminated, self.truncated)
+            if self._routed:
+                self._epilogue()
             return
         self.lib.so100_step(self._handle, ctypes.byref(self._buf), self._flags, self._stream())
 
@@ -642,19 +790,36 @@ class SO100VecEnv:
               "elapsed": self.elapsed.clone(), "episode": self.episode.clone()}
         if self._ee_ctrl is not None:
             st["ee_joint_target"] = self.ee_joint_target.clone()
+        if self._act:
+            st["actuation"] = {"hist": self.act_hist.clone(), "head": self.act_head.clone(),
+                               "params": self.act_params.clone(), "applied": self.actions.clone()}
         return st
 
-    def set_state(self, qpos, qvel, qacc_warmstart=None, elapsed=None, episode=None, ee_joint_target=None):
+    def set_state(self, qpos, qvel, qacc_warmstart=None, elapsed=None, episode=None, ee_joint_target=None,
+                  actuation=None):
         """action_mode="ee_delta": ee_joint_target [N,5] restores the commanded joint targets (from ``get_state``);
-        without it every command starts again from the new qpos.  ValueError in joint mode."""
+        without it every command starts again from the new qpos.  ValueError in joint mode.  With the actuation model,
+        actuation (``get_state()["actuation"]``: the command ring, head, act_params and the applied action) restores the
+        actuators; without it every actuator starts again from the new qpos with the parameters it has.  ValueError
+        without the model.  When both prologues run and only one state is given, both start again from the new qpos
+        (they share ``reinit``).  With per_episode the physical parameters are drawn again from the episode counters
+        given."""
         torch = _torch()
         if ee_joint_target is not None and self._ee_ctrl is None:
             raise ValueError("ee_joint_target needs action_mode='ee_delta'")
-        if self._ee_ctrl is not None:
-            if ee_joint_target is None:
+        if actuation is not None and not self._act:
+            raise ValueError("actuation state needs domain_randomization['actuation']")
+        if self._routed:
+            if ee_joint_target is not None:
+                self.ee_joint_target.copy_(torch.as_tensor(ee_joint_target, dtype=torch.float32))
+            if actuation is not None:
+                self.act_hist.copy_(torch.as_tensor(actuation["hist"], dtype=torch.float32))
+                self.act_head.copy_(torch.as_tensor(actuation["head"], dtype=torch.int32))
+                self.act_params.copy_(torch.as_tensor(actuation["params"], dtype=torch.float32))
+                self.actions.copy_(torch.as_tensor(actuation["applied"], dtype=torch.float32))
+            if (self._ee_ctrl is not None and ee_joint_target is None) or (self._act and actuation is None):
                 self.reinit.fill_(1)
             else:
-                self.ee_joint_target.copy_(torch.as_tensor(ee_joint_target, dtype=torch.float32))
                 self.reinit.zero_()
             self._reinit_pending = True
         self.qpos.copy_(torch.as_tensor(qpos, dtype=torch.float32))
@@ -665,6 +830,8 @@ class SO100VecEnv:
             self.elapsed.copy_(torch.as_tensor(elapsed, dtype=torch.int32))
         if episode is not None:
             self.episode.copy_(torch.as_tensor(episode, dtype=torch.int32))
+            if self._dr_per_episode:                 # (the actuator records restored above stay what they are)
+                self._dr_sample(None, None, keep_act=actuation is not None)
 
     # standalone ops exposed for parity tests
     def eval_reward(self, task, cube_site, ee_site, pair_bits):

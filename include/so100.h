@@ -453,6 +453,53 @@ int so100_ee_action(so100_env* env, const so100_ee_ctrl* ctrl, const float* qpos
  * jac[n,3,5] = its positional Jacobian over joints 0..4 (the roll column is written: it is 0 up to rounding). */
 int so100_ee_jacobian(so100_env* env, int n, const float* qpos, float* ee, float* jac, void* stream);
 
+/* ---- (additions to ABI 25) per-episode physical randomisation and an actuation-latency model: two
+ * launches beside the untouched step.  so100_dr_sample rewrites the dr_params rows so100_step reads (and draws each
+ * env's actuator record); so100_actuate turns the commanded action into the applied one the step then takes. */
+#define SO100_ACT_MAX_DELAY 7          /* control steps; the command ring holds SO100_ACT_HIST = 8 */
+#define SO100_ACT_HIST 8
+typedef struct so100_dr_ranges {
+  uint32_t size;          /* sizeof(so100_dr_ranges): the callee rejects a mismatch */
+  uint32_t reserved0;
+  uint64_t seed;
+  float   mass[2];        /* [lo, hi] of the cube mass scale, finite, > 0 */
+  float   friction[2];    /* [lo, hi] of the contact friction scale, finite, > 0 */
+  int32_t delay[2];       /* [lo, hi] of the actuation delay in control steps, 0..SO100_ACT_MAX_DELAY */
+  float   smoothing[2];   /* [lo, hi] of the first-order smoothing factor alpha, in (0, 1]; 1 = none */
+  float   rate[2];        /* [lo, hi] of the slew limit per control step in normalised action units, finite, > 0; >= 2 = none */
+} so100_dr_ranges;
+int so100_dr_ranges_bytes(void);
+/* Draw, on the device, dr_params[i][0:2] = (mass, friction) and / or act_params[i] = (delay, alpha, rate, 0) of the envs
+ * whose byte in mask_a or mask_b is non-zero (device [N] each; both NULL = all).  Every draw is so100_views_sample's
+ * U[0,1) of (seed, global env id = env_offset + i, episode[i], field): fields 1 mass, 2 friction, 4 delay, 5 smoothing,
+ * 6 rate.  Real values: clip(lo + (hi - lo) u, lo, hi) in float32; the delay, with h the 64-bit hash behind u (u = (h >>
+ * 40) / 2^24): lo + (((h >> 40) * (hi - lo + 1)) >> 24), stored as a float.  dr_params[i][2:4] (the action-noise sigma
+ * and the spare column) and the rows outside the masks are not written.  episode: device uint32 [N] or NULL = 0.  One
+ * launch on `stream`, no allocation, no synchronisation.  Nonzero (text in so100_last_error), before any device work and
+ * with nothing written: NULL ranges, a wrong `size` (checked first), a NULL env, both outputs NULL, a mass, friction or
+ * rate range that is not finite, not positive or inverted, a delay range outside 0..SO100_ACT_MAX_DELAY or inverted, a
+ * smoothing range outside (0, 1] or inverted. */
+int so100_dr_sample(so100_env* env, const so100_dr_ranges* ranges, const uint32_t* episode /* [N] or NULL */,
+                    const uint8_t* mask_a /* [N] or NULL */, const uint8_t* mask_b /* [N] or NULL */,
+                    float* dr_params /* [N,4] or NULL */, float* act_params /* [N,4] or NULL */, void* stream);
+/* The actuator model, one launch before so100_step.  State per env: hist [SO100_ACT_HIST][N][6] (slot-major: the ring of
+ * the last 8 clipped commands), head [N] (calls since the last re-initialisation) and action [N,6] itself, the applied
+ * action y of the last call, which is the step's action input.  Per env i and component c, with u = clip(command, -1, 1),
+ * (d, alpha, r) = act_params[i][0:3] and [lo_c, hi_c] the model's action range:
+ *   1. reinit[i] != 0: hold_c = clip(2 (qpos_c - lo_c) / (hi_c - lo_c) - 1, -1, 1) (the command that holds the measured
+ *      pose, so100_ee_action's step 6); every ring slot <- hold, y <- hold, head <- 0;
+ *   2. hist[head mod 8] <- u; v = hist[(head - d) mod 8]; head <- head + 1   (while head < d the slot read holds `hold`);
+ *   3. w = v if alpha == 1, else y + alpha (v - y);
+ *   4. y <- w if |w - y| <= r, else y + copysign(r, w - y);
+ *   5. action[i][c] <- y.
+ * With d = 0, alpha = 1 and r >= 2 the applied action is clip(command) bit for bit.  float32.  Nonzero (text in
+ * so100_last_error) before any device work, every output untouched: a NULL env, qpos, command, act_params, hist, head or
+ * action, a model with ee = 1 (its input is the mocap pose). */
+int so100_actuate(so100_env* env, const float* qpos /* [N,13] */, const float* command /* [N,6] */,
+                  const uint8_t* reinit /* [N] or NULL */, const float* act_params /* [N,4] */,
+                  float* hist /* [8][N][6] in/out */, int32_t* head /* [N] in/out */, float* action /* [N,6] in/out */,
+                  void* stream);
+
 /* Batched sparse GoalEnv reward (env.py:341-353): out[i] = ||a_i - d_i|| < threshold ? 0 : -1. */
 int so100_goal_reward(so100_env* env, int n, const float* achieved, const float* desired, float* out,
                       void* stream);
