@@ -64,6 +64,13 @@ hipError_t launch_dr_sample(const so100_dr_ranges&, const uint32_t*, const uint8
                             int, hipStream_t);
 hipError_t launch_actuate(const DevModel*, int, const float*, const float*, const uint8_t*, const float*, float*,
                           int32_t*, float*, hipStream_t);
+int norm_groups(int n);
+int norm_rows_per_group();
+int norm_max_groups();
+hipError_t launch_norm_update(const so100_norm&, int, const uint8_t*, double*, double*, hipStream_t);
+hipError_t launch_norm_apply(const so100_norm&, int, const uint8_t*, const double*, hipStream_t);
+hipError_t launch_norm_return(const so100_norm_ret&, int, const float*, const uint8_t*, const uint8_t*, double*, double*,
+                              double*, float*, hipStream_t);
 }  // namespace so100
 
 using so100::DevModel;
@@ -1637,6 +1644,80 @@ static int so100_actuate_impl(so100_env* env, const float* qpos, const float* co
   return e == hipSuccess ? 0 : fail_hip("so100_actuate", e);
 }
 
+// the checks so100_norm_update and so100_norm_apply share (include/so100.h): the record first, then the env and pointers
+static int norm_check(const char* fn, so100_env* env, const so100_norm* nm, int n, const void* stats, bool apply) {
+  char msg[160];
+  auto bad = [&](const char* what) {
+    snprintf(msg, sizeof(msg), "%s: %s", fn, what);
+    return fail(msg);
+  };
+  if (!nm) return bad("NULL norm");
+  if (nm->size != sizeof(so100_norm)) return size_mismatch(fn, "so100_norm", nm->size, sizeof(so100_norm));
+  if (nm->nsrc < 1 || nm->nsrc > SO100_NORM_MAX_SRC) return bad("nsrc outside 1..3");
+  long long total = 0;
+  for (int k = 0; k < nm->nsrc; k++) {
+    const so100_norm_src& s = nm->src[k];
+    if (s.dim < 1 || s.dim > SO100_NORM_MAX_DIM) return bad("dim outside 1..32");
+    if (s.offset < 0) return bad("offset < 0");
+    if ((long long)s.stride < (long long)s.offset + s.dim) return bad("stride smaller than offset + dim");
+    if (apply && s.y_stride < s.dim) return bad("y_stride smaller than dim");
+    total += s.dim;
+  }
+  if (total > SO100_NORM_MAX_DIM) return bad("total dim outside 1..32");
+  if (!(std::isfinite(nm->epsilon) && nm->epsilon > 0.0)) return bad("epsilon must be finite and > 0");
+  if (!(std::isfinite(nm->clip) && nm->clip > 0.0)) return bad("clip must be finite and > 0");
+  if (nm->flags & ~SO100_NORM_INVERSE) return bad("unknown flags");
+  if (n < 0) return bad("n < 0");
+  if (!env) return bad("NULL env");
+  for (int k = 0; k < nm->nsrc; k++) {
+    if (!nm->src[k].x) return bad("NULL source");
+    if (apply && !nm->src[k].y) return bad("NULL output");
+  }
+  if (!stats) return bad("NULL stats");
+  return 0;
+}
+
+static int so100_norm_update_impl(so100_env* env, const so100_norm* nm, int n, const uint8_t* mask, double* stats,
+                                  void* work, void* stream) {
+  if (int rc = norm_check("so100_norm_update", env, nm, n, stats, false)) return rc;
+  if (!work) return fail("so100_norm_update: NULL work");
+  if (n == 0) return 0;
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_norm_update(*nm, n, mask, stats, (double*)work, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip("so100_norm_update", e);
+}
+
+static int so100_norm_apply_impl(so100_env* env, const so100_norm* nm, int n, const uint8_t* mask, const double* stats,
+                                 void* stream) {
+  if (int rc = norm_check("so100_norm_apply", env, nm, n, stats, true)) return rc;
+  if (n == 0) return 0;
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_norm_apply(*nm, n, mask, stats, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip("so100_norm_apply", e);
+}
+
+static int so100_norm_return_impl(so100_env* env, const so100_norm_ret* a, int n, const float* reward,
+                                  const uint8_t* terminated, const uint8_t* truncated, double* ret, double* stats,
+                                  void* work, float* reward_norm, void* stream) {
+  if (!a) return fail("so100_norm_return: NULL args");
+  if (a->size != sizeof(so100_norm_ret))
+    return size_mismatch("so100_norm_return", "so100_norm_ret", a->size, sizeof(so100_norm_ret));
+  if (!(a->gamma > 0.0 && a->gamma <= 1.0)) return fail("so100_norm_return: gamma outside (0, 1]");      // false for NaN
+  if (!(std::isfinite(a->epsilon) && a->epsilon > 0.0)) return fail("so100_norm_return: epsilon must be finite and > 0");
+  if (!(std::isfinite(a->clip) && a->clip > 0.0)) return fail("so100_norm_return: clip must be finite and > 0");
+  if (a->flags & ~(SO100_NORM_RET_UPDATE | SO100_NORM_RET_NORMALIZE)) return fail("so100_norm_return: unknown flags");
+  if (n < 0) return fail("so100_norm_return: n < 0");
+  if (!env) return fail("so100_norm_return: NULL env");
+  if (!reward || !ret || !stats) return fail("so100_norm_return: NULL reward, ret or stats");
+  if ((a->flags & SO100_NORM_RET_UPDATE) && !work) return fail("so100_norm_return: NULL work");
+  if ((a->flags & SO100_NORM_RET_NORMALIZE) && !reward_norm) return fail("so100_norm_return: NULL reward_norm");
+  if (n == 0) return 0;
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_norm_return(*a, n, reward, terminated, truncated, ret, stats, (double*)work, reward_norm,
+                                           (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip("so100_norm_return", e);
+}
+
 // the step kernels' hull support for n directions of one hull (device buffers; the null stream, waited for)
 static int so100_hull_support_probe_impl(so100_env* env, int hull, const float* dirs, int n, int use_cells, float* out) {
   if (!env || !dirs || !out || n < 0) return fail("so100_hull_support_probe: bad arguments");
@@ -1685,6 +1766,52 @@ int so100_actuate(so100_env* env, const float* qpos, const float* command, const
     return so100_actuate_impl(env, qpos, command, reinit, act_params, hist, head, action, stream);
   } catch (...) {
     return caught("so100_actuate");
+  }
+}
+
+int so100_norm_bytes(void) { return (int)sizeof(so100_norm); }
+int so100_norm_ret_bytes(void) { return (int)sizeof(so100_norm_ret); }
+
+int so100_norm_limits(int* rows_per_group, int* max_groups) {
+  if (!rows_per_group || !max_groups) return fail("so100_norm_limits: NULL argument");
+  *rows_per_group = so100::norm_rows_per_group();
+  *max_groups = so100::norm_max_groups();
+  return 0;
+}
+
+int so100_norm_work_bytes(int n) {
+  if (n < 0) {
+    fail("so100_norm_work_bytes: n < 0");
+    return -1;
+  }
+  return so100::norm_groups(n) * 3 * SO100_NORM_MAX_DIM * (int)sizeof(double);
+}
+
+int so100_norm_update(so100_env* env, const so100_norm* norm, int n, const uint8_t* mask, double* stats, void* work,
+                      void* stream) {
+  try {
+    return so100_norm_update_impl(env, norm, n, mask, stats, work, stream);
+  } catch (...) {
+    return caught("so100_norm_update");
+  }
+}
+
+int so100_norm_apply(so100_env* env, const so100_norm* norm, int n, const uint8_t* mask, const double* stats,
+                     void* stream) {
+  try {
+    return so100_norm_apply_impl(env, norm, n, mask, stats, stream);
+  } catch (...) {
+    return caught("so100_norm_apply");
+  }
+}
+
+int so100_norm_return(so100_env* env, const so100_norm_ret* args, int n, const float* reward, const uint8_t* terminated,
+                      const uint8_t* truncated, double* ret, double* stats, void* work, float* reward_norm,
+                      void* stream) {
+  try {
+    return so100_norm_return_impl(env, args, n, reward, terminated, truncated, ret, stats, work, reward_norm, stream);
+  } catch (...) {
+    return caught("so100_norm_return");
   }
 }
 

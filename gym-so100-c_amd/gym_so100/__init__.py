@@ -5,7 +5,7 @@
 * Registration of the reference's env ids when gymnasium is importable (reference __init__.py:4-32), and
   ``gym_so100.make(id, **kwargs)``, the same construction (SO100Env + TimeLimit) where it is not.
 """
-from .vec_env import SO100VecEnv  # noqa: F401
+from .vec_env import SO100VecEnv, merge_normalize_states  # noqa: F401
 from .env import SO100Env, SO100GoalEnv  # noqa: F401
 
 ENV_IDS = {

@@ -155,6 +155,51 @@ class SO100DrRanges(ctypes.Structure):
         self.rate[:] = [float(x) for x in rate]
 
 
+SO100_NORM_MAX_DIM = 32            # include/so100.h: the columns one normaliser call carries
+SO100_NORM_MAX_SRC = 3
+SO100_NORM_INVERSE = 1
+SO100_NORM_RET_UPDATE = 1
+SO100_NORM_RET_NORMALIZE = 2
+
+
+class SO100NormSrc(ctypes.Structure):
+    """Mirror of ``so100_norm_src`` (include/so100.h): rows of float32 at (x, stride, offset, dim) and where
+    ``so100_norm_apply`` writes them (y, y_stride)."""
+    _fields_ = [("x", ctypes.c_void_p), ("y", ctypes.c_void_p), ("stride", ctypes.c_int32), ("offset", ctypes.c_int32),
+                ("dim", ctypes.c_int32), ("y_stride", ctypes.c_int32)]
+
+
+class SO100Norm(ctypes.Structure):
+    """Mirror of ``so100_norm`` (include/so100.h): the sources and constants of one ``so100_norm_update`` /
+    ``so100_norm_apply`` call.  ``sources``: up to three (x pointer, stride, offset, dim, y pointer, y_stride) tuples;
+    ``size`` is set to the mirror's size, which the callee checks against its own."""
+    _fields_ = [("size", ctypes.c_uint32), ("nsrc", ctypes.c_int32), ("epsilon", ctypes.c_double),
+                ("clip", ctypes.c_double), ("flags", ctypes.c_uint32), ("reserved0", ctypes.c_uint32),
+                ("src", SO100NormSrc * SO100_NORM_MAX_SRC)]
+
+    def __init__(self, sources=(), epsilon=1e-8, clip=10.0, flags=0):
+        super().__init__()
+        self.size = ctypes.sizeof(SO100Norm)
+        self.nsrc = len(sources)
+        self.epsilon, self.clip, self.flags = float(epsilon), float(clip), int(flags)
+        for k, (x, stride, offset, dim, y, y_stride) in enumerate(list(sources)[:SO100_NORM_MAX_SRC]):
+            s = self.src[k]
+            s.x, s.y = x, y
+            s.stride, s.offset, s.dim, s.y_stride = int(stride), int(offset), int(dim), int(y_stride)
+
+
+class SO100NormRet(ctypes.Structure):
+    """Mirror of ``so100_norm_ret`` (include/so100.h): the constants of one ``so100_norm_return`` call."""
+    _fields_ = [("size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("gamma", ctypes.c_double),
+                ("epsilon", ctypes.c_double), ("clip", ctypes.c_double)]
+
+    def __init__(self, flags=0, gamma=0.99, epsilon=1e-8, clip=10.0):
+        super().__init__()
+        self.size = ctypes.sizeof(SO100NormRet)
+        self.flags = int(flags)
+        self.gamma, self.epsilon, self.clip = float(gamma), float(epsilon), float(clip)
+
+
 SO100_NMATERIAL = 5
 
 
@@ -265,6 +310,13 @@ def load():
     lib.so100_dr_ranges_bytes.argtypes = []
     lib.so100_dr_sample.argtypes = [_P, ctypes.POINTER(SO100DrRanges), _P, _P, _P, _P, _P, _P]
     lib.so100_actuate.argtypes = [_P, _P, _P, _P, _P, _P, _P, _P, _P]
+    lib.so100_norm_bytes.argtypes = []
+    lib.so100_norm_ret_bytes.argtypes = []
+    lib.so100_norm_limits.argtypes = [_P, _P]
+    lib.so100_norm_work_bytes.argtypes = [ctypes.c_int]
+    lib.so100_norm_update.argtypes = [_P, ctypes.POINTER(SO100Norm), ctypes.c_int, _P, _P, _P, _P]
+    lib.so100_norm_apply.argtypes = [_P, ctypes.POINTER(SO100Norm), ctypes.c_int, _P, _P, _P]
+    lib.so100_norm_return.argtypes = [_P, ctypes.POINTER(SO100NormRet), ctypes.c_int, _P, _P, _P, _P, _P, _P, _P, _P]
     lib.so100_hull_cells.argtypes = [_P, _P, _P, ctypes.c_int]
     lib.so100_hull_blocks.argtypes = [_P, _P, ctypes.c_int]
     lib.so100_hull_support_probe.argtypes = [_P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P]
@@ -285,7 +337,9 @@ def load():
                "so100_render_aux", "so100_cams_bytes", "so100_render_cams", "so100_shadow_bytes",
                "so100_render_casters", "so100_render_shadow", "so100_msaa_bytes", "so100_render_msaa",
                "so100_ee_ctrl_bytes", "so100_ee_action", "so100_ee_jacobian", "so100_hull_blocks",
-               "so100_hull_support_probe", "so100_dr_ranges_bytes", "so100_dr_sample", "so100_actuate"):
+               "so100_hull_support_probe", "so100_dr_ranges_bytes", "so100_dr_sample", "so100_actuate",
+               "so100_norm_bytes", "so100_norm_ret_bytes", "so100_norm_limits", "so100_norm_work_bytes",
+               "so100_norm_update", "so100_norm_apply", "so100_norm_return"):
         getattr(lib, fn).restype = ctypes.c_int
     lib.so100_struct_sizes.argtypes = [_P, _P]
     lib.so100_struct_sizes.restype = ctypes.c_int
@@ -318,8 +372,19 @@ def load():
     if lib.so100_dr_ranges_bytes() != ctypes.sizeof(SO100DrRanges):
         raise NativeLibraryError(f"struct layout mismatch: so100_dr_ranges {lib.so100_dr_ranges_bytes()} vs "
                                  f"{ctypes.sizeof(SO100DrRanges)}")
+    if lib.so100_norm_bytes() != ctypes.sizeof(SO100Norm) or lib.so100_norm_ret_bytes() != ctypes.sizeof(SO100NormRet):
+        raise NativeLibraryError(f"struct layout mismatch: so100_norm {lib.so100_norm_bytes()} vs "
+                                 f"{ctypes.sizeof(SO100Norm)}, so100_norm_ret {lib.so100_norm_ret_bytes()} vs "
+                                 f"{ctypes.sizeof(SO100NormRet)}")
     _lib = lib
     return lib
+
+
+def norm_limits():
+    """(rows a workgroup of the moments kernel takes below the grid cap, the grid cap) (so100_norm_limits)."""
+    r, g = ctypes.c_int(0), ctypes.c_int(0)
+    check(load().so100_norm_limits(ctypes.byref(r), ctypes.byref(g)), "so100_norm_limits")
+    return r.value, g.value
 
 
 EXPORTED_SYMBOLS = ("so100_abi_version", "so100_last_error", "so100_source_hash", "so100_struct_sizes", "so100_create", "so100_destroy", "so100_num_envs",
@@ -334,7 +399,9 @@ EXPORTED_SYMBOLS = ("so100_abi_version", "so100_last_error", "so100_source_hash"
                     "so100_render_aux", "so100_cams_bytes", "so100_render_cams", "so100_shadow_bytes",
                     "so100_render_casters", "so100_render_shadow", "so100_msaa_bytes", "so100_render_msaa",
                     "so100_ee_ctrl_bytes", "so100_ee_action", "so100_ee_jacobian", "so100_hull_blocks",
-                    "so100_hull_support_probe", "so100_dr_ranges_bytes", "so100_dr_sample", "so100_actuate")
+                    "so100_hull_support_probe", "so100_dr_ranges_bytes", "so100_dr_sample", "so100_actuate",
+                    "so100_norm_bytes", "so100_norm_ret_bytes", "so100_norm_limits", "so100_norm_work_bytes",
+                    "so100_norm_update", "so100_norm_apply", "so100_norm_return")
 
 
 def source_hash():

@@ -44,6 +44,15 @@ the Cartesian delta (dx, dy, dz, droll, grip) a device prologue turns into the j
 parameters drawn again for every new episode; a per-env actuation delay, smoothing and slew limit between the action and
 the step): both run on the device, and the adapter's contract does not change.
 
+``normalize=True`` (or a dict, normalize.NORMALIZE_DEFAULTS) is forwarded to the env and replaces the scripts'
+``VecNormalize(env, norm_obs=True, norm_reward=False, clip_obs=10.0)`` line: the running statistics live and are applied
+on the device, and the adapter hands out the normalised observations, rewards and
+``terminal_observation``.  It carries VecNormalize's surface: ``obs_rms`` / ``ret_rms`` (assignable:
+``eval_env.obs_rms = train_env.obs_rms``), ``training``, ``norm_reward``, ``get_original_obs()``,
+``get_original_reward()``, ``normalize_obs`` / ``unnormalize_obs`` (numpy) and ``save(path)`` / ``load_stats(path)``
+(an ``.npz`` of the env's ``normalize_state()``; not SB3's pickle).  With pixel observations only ``agent_pos`` is
+normalised, and nothing more is copied to the host than without the option.
+
 The image (or flattened) tensor reaches the host by one asynchronous copy into pinned memory and one stream
 synchronisation per step.  Two pinned buffers alternate: **the image array of an observation returned by
 ``reset()`` / ``step()`` stays valid through the next ``step()`` and is overwritten by the one after it** (SB3's
@@ -74,9 +83,10 @@ class SO100SB3VecEnv(_VecEnvBase):
     def __init__(self, num_envs, task="so100_cube_to_bin", device="cuda:0", seed=0, max_episode_steps=None,
                  domain_randomization=None, env_offset=0, iterations=None, solver="newton", obs_type="so100_state",
                  observation_width=640, observation_height=480, channels_first=False, cameras=None, shadows=False,
-                 antialias=False, action_mode="joint", ee_control=None):
+                 antialias=False, action_mode="joint", ee_control=None, normalize=None):
         self.pixel_obs = obs_type == "so100_pixels_agent_pos"
         kw = {}
+        self._last_obs = None                      # the observation last returned (get_original_obs: its image)
         if shadows and not self.pixel_obs:
             raise ValueError("shadows need obs_type='so100_pixels_agent_pos'")
         if antialias and not self.pixel_obs:
@@ -102,6 +112,8 @@ class SO100SB3VecEnv(_VecEnvBase):
             raise ValueError("channels_first needs obs_type='so100_pixels_agent_pos'")
         if action_mode != "joint" or ee_control is not None:      # the env's own checks (ValueError) apply
             kw["action_mode"], kw["ee_control"] = action_mode, ee_control
+        if normalize is not None:                                  # the env's own checks (ValueError) apply
+            kw["normalize"] = normalize
         self.venv = SO100VecEnv(num_envs, task=task, device=device, seed=seed, max_episode_steps=max_episode_steps,
                                 autoreset=True, domain_randomization=domain_randomization, env_offset=env_offset,
                                 iterations=iterations, solver=solver, episode_stats=True, **kw)
@@ -186,9 +198,16 @@ class SO100SB3VecEnv(_VecEnvBase):
         infos = [{"is_success": bool(success[i])} for i in range(self.num_envs)]
         idx = np.flatnonzero(dones)
         if idx.size:
-            final = _np(v.final_obs[done_t])
-            if v.is_goal:
-                fgoal = _np(prev_goal[done_t])
+            fachieved = None
+            if v.final_obs_norm is None:
+                final = _np(v.final_obs[done_t])
+                if v.is_goal:
+                    fgoal = _np(prev_goal[done_t])
+            else:                                            # normalize: the finished rows, normalised on the device
+                final = _np(v.final_obs_norm[done_t])        # (pixel observations: [.,6], agent_pos alone)
+                if v.is_goal:
+                    g = v.normalize_obs({"achieved_goal": v.final_obs[done_t][:, 0:3], "desired_goal": prev_goal[done_t]})
+                    fachieved, fgoal = _np(g["achieved_goal"]), _np(g["desired_goal"])
             if self.pixel_obs:
                 fpix = _np(v.final_pixels[done_t])           # only the done envs' images, gathered on the device
                 if v.camera_names is not None and not v.is_goal:
@@ -201,9 +220,11 @@ class SO100SB3VecEnv(_VecEnvBase):
                     term_obs = {"observation": fflat[k], "achieved_goal": final[k, 0:3].copy(),
                                 "desired_goal": fgoal[k]}
                 elif self.pixel_obs:
-                    term_obs = {"pixels": fpix[k], "agent_pos": final[k, 9:15].copy()}
+                    term_obs = {"pixels": fpix[k],
+                                "agent_pos": (final[k, 9:15] if v.final_obs_norm is None else final[k]).copy()}
                 elif v.is_goal:
-                    term_obs = {"observation": final[k], "achieved_goal": final[k, 0:3].copy(),
+                    term_obs = {"observation": final[k],
+                                "achieved_goal": final[k, 0:3].copy() if fachieved is None else fachieved[k],
                                 "desired_goal": fgoal[k]}
                 else:
                     term_obs = final[k]
@@ -276,8 +297,95 @@ class SO100SB3VecEnv(_VecEnvBase):
     def env_is_wrapped(self, wrapper_class, indices=None):
         return [False for _ in self._indices(indices)]
 
+    # ------------------------------------------------------------------ VecNormalize's surface (normalize=...)
+    @property
+    def obs_rms(self):
+        """key -> .mean / .var / .count (the state env's single key: that object itself, as VecNormalize's obs_rms)"""
+        rms = self.venv.obs_rms
+        return rms["obs"] if set(rms) == {"obs"} else rms
+
+    @obs_rms.setter
+    def obs_rms(self, rms):
+        self.venv.obs_rms = rms
+
+    @property
+    def ret_rms(self):
+        return self.venv.ret_rms
+
+    @ret_rms.setter
+    def ret_rms(self, rms):
+        self.venv.ret_rms = rms
+
+    @property
+    def training(self):
+        return self.venv.training
+
+    @training.setter
+    def training(self, on):
+        self.venv.training = on
+
+    @property
+    def norm_obs(self):
+        return self.venv.obs_norm is not None or self.venv.agent_pos_norm is not None
+
+    @property
+    def norm_reward(self):
+        return self.venv.reward_norm is not None
+
+    def get_original_obs(self):
+        """The raw observation behind the last one returned (read from the device now: valid until the next step)."""
+        v = self.venv
+        v._normalizer()
+        if self.pixel_obs:
+            out = dict(self._last_obs)
+            out["agent_pos"] = _np(v.obs[:, 9:15])
+            return out
+        if v.is_goal:
+            return {"observation": _np(v.obs), "achieved_goal": _np(v.achieved_goal), "desired_goal": _np(v.desired_goal)}
+        return _np(v.obs)
+
+    def get_original_reward(self):
+        """The raw rewards of the last step."""
+        self.venv._normalizer()
+        return _np(self.venv.reward).astype(np.float32)
+
+    def _to_device(self, obs):
+        import torch
+        if isinstance(obs, dict):
+            return {k: (torch.as_tensor(np.ascontiguousarray(x), dtype=torch.float32, device=self.venv.device)
+                        if k in self.venv._normalizer().cols else x) for k, x in obs.items()}
+        return torch.as_tensor(np.ascontiguousarray(obs), dtype=torch.float32, device=self.venv.device)
+
+    def _to_host(self, obs):
+        if isinstance(obs, dict):
+            return {k: (_np(x) if hasattr(x, "detach") else x) for k, x in obs.items()}
+        return _np(obs)
+
+    def normalize_obs(self, obs):
+        """numpy (or a dict of numpy) -> the normalised observation, by the device kernel, with the current statistics"""
+        return self._to_host(self.venv.normalize_obs(self._to_device(obs)))
+
+    def unnormalize_obs(self, obs):
+        return self._to_host(self.venv.unnormalize_obs(self._to_device(obs)))
+
+    def save(self, path):
+        """The statistics and options as an ``.npz`` (``normalize_state()``), bit for bit."""
+        with open(path, "wb") as f:
+            np.savez(f, **self.venv.normalize_state())
+
+    def load_stats(self, path):
+        """Take the statistics ``save`` wrote (the options stay this env's)."""
+        with np.load(path) as z:
+            self.venv.set_normalize_state({k: z[k] for k in z.files})
+
     # ------------------------------------------------------------------ helpers
     def _obs_np(self, obs):
+        out = self._obs_np_inner(obs)
+        if self.venv._norm is not None:            # (get_original_obs hands the image of this observation back)
+            self._last_obs = out
+        return out
+
+    def _obs_np_inner(self, obs):
         if self._host is not None:
             # the large tensor: one asynchronous copy into the pinned buffer of this step, one synchronisation
             import torch

@@ -33,6 +33,7 @@ import numpy as np
 from . import _native
 from .model import NOBS, NQ, NV, build_model
 from .constants import GOAL_MAX_EPISODE_STEPS
+from .normalize import Normalizer, merge_normalize_states, normalize_options  # noqa: F401  (re-exported)
 
 _MAX_STEPS = {"so100_cube_to_bin": 700, "so100_touch_cube": 300, "so100_touch_cube_sparse": 300,
               "so100_goal": GOAL_MAX_EPISODE_STEPS}
@@ -160,6 +161,11 @@ def physical_dr_options(dr, variant="joint"):
         _real_range("domain_randomization: friction", dr.get("friction", (0.8, 1.2)))
 
 
+class NormalizeOffError(AttributeError, ValueError):
+    """The normalisation attributes of an env built without normalize=...: a ValueError for callers, an AttributeError
+    so that ``hasattr(env, "obs_rms")`` is False."""
+
+
 class SO100VecEnv:
     """N parallel SO-ARM100 envs on one GPU.
 
@@ -252,6 +258,20 @@ class SO100VecEnv:
         ee_control: None or a dict overriding EE_CONTROL_DEFAULTS (iters, pos_scale, rot_scale, damping, dq_max,
             lead_max, ws_lo, ws_hi; the workspace box defaults to the table's x / y extent and z in [0, 0.6]); unknown
             keys and out-of-range values raise ValueError before any device use.  action_mode="ee_delta" only.
+        normalize: None (default: every call what it is without the argument), True or a dict overriding
+            normalize.NORMALIZE_DEFAULTS (obs, reward, clip_obs, clip_reward, gamma, epsilon, training): SB3
+            VecNormalize's running normalisation, on the device (csrc/so100_norm.hip, include/so100.h
+            so100_norm_update).  True is the reference scripts' setting: observations on, rewards off,
+            clip 10.  Running float64 mean / variance / count per column, updated after every ``step`` / ``reset`` with
+            the observations returned (while ``training``), with no host synchronisation.  ``step`` / ``reset`` then
+            return the normalised observation (state env: ``obs_norm`` [N,15]; GoalEnv: ``observation``,
+            ``achieved_goal`` and ``desired_goal``, one set of statistics each; pixel observations: ``agent_pos`` only,
+            images are never touched) and, with ``reward=True``, ``reward_norm`` = clip(reward / sqrt(var of the
+            discounted return)); ``info["final_observation"]`` is normalised with the same statistics and never enters
+            them.  The raw tensors (``obs``, ``reward``, ``final_obs``, ``achieved_goal``, ``desired_goal``) stay what
+            they are.  ``training`` (settable), ``obs_rms``, ``ret_rms``, ``normalize_obs``, ``unnormalize_obs``,
+            ``normalize_state`` and ``set_normalize_state`` below.  ValueError for unknown keys and bad values, and for
+            the GoalEnv's flattened pixel observation (thousands of columns: not normalised).
     """
 
     def __init__(self, num_envs, task="so100_cube_to_bin", obs_type="so100_state", device="cuda:0", seed=0,
@@ -259,8 +279,13 @@ class SO100VecEnv:
                  iterations=None, debug=False, solver="newton", observation_width=640, observation_height=480,
                  variant="joint", reward64=False, nsubstep=None, convex="epa", episode_stats=False, channels_first=False,
                  flat_pixels=False, depth=False, segmentation=False, cameras=None, shadows=False,
-                 antialias=False, action_mode="joint", ee_control=None):
+                 antialias=False, action_mode="joint", ee_control=None, normalize=None):
         torch = _torch()
+        norm_options = normalize_options(normalize)      # its ValueErrors before any device work
+        if norm_options is not None and norm_options["obs"] and task == "so100_goal" \
+                and obs_type == "so100_pixels_agent_pos":
+            raise ValueError("normalize: the GoalEnv's flattened pixel observation ([N, 3HW+6]) is not normalised; use "
+                             "normalize=dict(obs=False, ...) or the state observation")
         if action_mode not in ACTION_MODES:
             raise ValueError(f"action_mode {action_mode!r}: one of {ACTION_MODES}")
         if action_mode == "ee_delta":
@@ -355,6 +380,9 @@ class SO100VecEnv:
             self._reinit_pending = True                                      # host side: some byte of reinit may be set
         self._routed = self._ee_ctrl is not None       # a prologue writes ``actions``: the step never reads an action buffer
         self._pre = self._routed                       # a step is more than the so100_step launch
+        self._norm = None                              # the running normaliser (normalize=...), built below
+        self.obs_norm = self.reward_norm = self.final_obs_norm = None
+        self.achieved_goal_norm = self.desired_goal_norm = self.agent_pos_norm = None
         self.obs = torch.zeros(n, NOBS, dtype=f32, device=d)
         self.reward = torch.zeros(n, dtype=f32, device=d)
         self.terminated = torch.zeros(n, dtype=torch.bool, device=d)
@@ -416,6 +444,22 @@ class SO100VecEnv:
             if flat_pixels:
                 self._npix = 3 * self.renderer.width * self.renderer.height * (1 if cameras is None else len(cameras))
                 self.pixels_flat = torch.zeros(n, self._npix + 6, dtype=f32, device=d)
+        if norm_options is not None:
+            if self.renderer is not None:
+                keys = [("agent_pos", self.obs, 9, 6)]
+            elif self.is_goal:
+                keys = [("observation", self.obs, 0, NOBS), ("achieved_goal", self.achieved_goal, 0, 3),
+                        ("desired_goal", self.desired_goal, 0, 3)]
+            else:
+                keys = [("obs", self.obs, 0, NOBS)]
+            self._norm = Normalizer(self, norm_options, keys, final_src=self.final_obs if self.autoreset else None)
+            out = self._norm.out
+            self.obs_norm = out.get("obs", out.get("observation"))
+            self.agent_pos_norm = out.get("agent_pos")
+            self.achieved_goal_norm, self.desired_goal_norm = out.get("achieved_goal"), out.get("desired_goal")
+            self.final_obs_norm = self._norm.final_out      # [N,15], or the final agent_pos [N,6] with pixels
+            self.reward_norm = self._norm.reward_norm
+            self._pre = True
 
     # ------------------------------------------------------------------ plumbing
     def _fill_buffers(self):
@@ -543,7 +587,7 @@ class SO100VecEnv:
             self.reinit.fill_(1)                     # every actuator starts from its env's pose
             self._reinit_pending = True
         self._routed = self._ee_ctrl is not None or self._act
-        self._pre = self._routed or self._dr_per_episode
+        self._pre = self._routed or self._dr_per_episode or getattr(self, "_norm", None) is not None
         if self._dr_ranges is not None:
             self._dr_sample(None, None, act_only=not self._dr_per_episode)
         self._flags |= _native.SO100_FLAG_DR
@@ -600,6 +644,8 @@ class SO100VecEnv:
             if self._visual is not None and self._visual[1]:
                 self._sample_views(None if mask is None else self._mask)
             self._render_all()
+        if self._norm is not None:                       # the reset envs' observations enter the statistics
+            self._norm.after_reset(None if mask is None else self._mask)
         info = {"is_success": torch.zeros_like(self.success)}
         return self._observation(), info
 
@@ -636,19 +682,25 @@ class SO100VecEnv:
             done = self._step_pixels()
         if self._routed:
             self._epilogue()
+        if self._norm is not None:
+            self._norm.after_step()
         info = {"is_success": self.success, "diverged": self.diverged, "contact_bits": self.contact_bits,
                 "ncon_dropped": self.ncon_dropped}
         if self.autoreset:
-            info["final_observation"] = self.final_obs if self.renderer is None else self._with_aux(
-                {"pixels": self.final_pixels, "agent_pos": self.final_obs[:, 9:15]}, self.final_depth,
-                self.final_segmentation)
+            # (normalize: the rows of the envs that finished, normalised with the statistics as the step left them)
+            final = self.final_obs if self.final_obs_norm is None else self.final_obs_norm
+            info["final_observation"] = final if self.renderer is None else self._with_aux(
+                {"pixels": self.final_pixels,
+                 "agent_pos": self.final_obs[:, 9:15] if self.final_obs_norm is None else final},
+                self.final_depth, self.final_segmentation)
             info["_final_observation"] = done
         if self.is_goal:
             info["TimeLimit.truncated"] = self.truncated
         if self.ep_final is not None:                  # RecordEpisodeStatistics' info["episode"] / "_episode"
             info["episode"] = {"r": self.ep_final[:, 0], "l": self.ep_final[:, 1]}
             info["_episode"] = done
-        return self._observation(), self.reward, self.terminated, self.truncated, info
+        reward = self.reward if self.reward_norm is None else self.reward_norm
+        return self._observation(), reward, self.terminated, self.truncated, info
 
     def set_action_buffer(self, actions):
         """Point the kernel's action input at a resident [N,6] float32 device tensor (zero copy).
@@ -755,6 +807,8 @@ class SO100VecEnv:
                 self._dr_sample(self.terminated, self.truncated)
             if self._routed:
                 self._epilogue()
+            if self._norm is not None:
+                self._norm.after_step()
             return
         self.lib.so100_step(self._handle, ctypes.byref(self._buf), self._flags, self._stream())
 
@@ -769,10 +823,74 @@ class SO100VecEnv:
                 return self._with_aux({"observation": _torch().cat([flat, agent_pos], dim=1),
                                        "achieved_goal": self.achieved_goal, "desired_goal": self.desired_goal},
                                       self.depth, self.segmentation)
+            if self.agent_pos_norm is not None:
+                agent_pos = self.agent_pos_norm
             return self._with_aux({"pixels": self.pixels, "agent_pos": agent_pos}, self.depth, self.segmentation)
+        if self.obs_norm is not None:
+            if self.is_goal:
+                return {"observation": self.obs_norm, "achieved_goal": self.achieved_goal_norm,
+                        "desired_goal": self.desired_goal_norm}
+            return self.obs_norm
         if self.is_goal:
             return {"observation": self.obs, "achieved_goal": self.achieved_goal, "desired_goal": self.desired_goal}
         return self.obs
+
+    # ------------------------------------------------------------------ running normalisation (normalize=...)
+    # The properties and methods below go through _normalizer(): on an env built without normalize=... they raise
+    # NormalizeOffError from inside the property (so `env.training` raises rather than answering False, and
+    # hasattr(env, "obs_rms") is False, which the SB3 adapter's get_attr / set_attr rely on).
+    def _normalizer(self):
+        if self._norm is None:
+            raise NormalizeOffError("this env was built without normalize=...")
+        return self._norm
+
+    @property
+    def training(self):
+        """normalize: while True every ``step`` / ``reset`` updates the statistics; False freezes them (an eval env)"""
+        return self._normalizer().training
+
+    @training.setter
+    def training(self, on):
+        self._normalizer().training = bool(on)
+
+    @property
+    def obs_rms(self):
+        """normalize: key -> object with .mean / .var (float64 numpy) and .count, copied from the device on access (a
+        synchronisation).  Keys: "obs" (state env), "observation" / "achieved_goal" / "desired_goal" (GoalEnv),
+        "agent_pos" (pixel observations).  Assignable: ``eval_env.obs_rms = train_env.obs_rms``."""
+        return self._normalizer().obs_rms()
+
+    @obs_rms.setter
+    def obs_rms(self, rms):
+        self._normalizer().set_obs_rms(rms)
+
+    @property
+    def ret_rms(self):
+        """normalize: the discounted return's .mean / .var / .count, copied from the device on access"""
+        return self._normalizer().ret_rms()
+
+    @ret_rms.setter
+    def ret_rms(self, rms):
+        self._normalizer().set_ret_rms(rms)
+
+    def normalize_obs(self, obs):
+        """normalize: clip((obs - mean) / sqrt(var + epsilon)) with the current statistics, on the device (no update):
+        a float32 device tensor [..., dim] of the env's first key, or a dict by key (other keys pass through)"""
+        return self._normalizer().transform(obs)
+
+    def unnormalize_obs(self, obs):
+        """normalize: obs * sqrt(var + epsilon) + mean, the inverse of ``normalize_obs`` where it did not clip"""
+        return self._normalizer().transform(obs, inverse=True)
+
+    def normalize_state(self):
+        """normalize: the statistics as a plain dict of float64 numpy arrays ("<key>.mean" / ".var" / ".count", "ret.*")
+        plus the options, as ``np.savez(path, **state)`` stores it bit for bit"""
+        return self._normalizer().state()
+
+    def set_normalize_state(self, state):
+        """normalize: take the statistics of ``normalize_state()`` (another env's, a checkpoint's ``np.load``, or
+        ``merge_normalize_states`` of several shards'); the options stay this env's"""
+        self._normalizer().set_state(state)
 
     def compute_reward(self, achieved_goal, desired_goal, info=None):
         """Batched sparse GoalEnv reward on the device (env.py:341-353)."""
@@ -793,10 +911,12 @@ class SO100VecEnv:
         if self._act:
             st["actuation"] = {"hist": self.act_hist.clone(), "head": self.act_head.clone(),
                                "params": self.act_params.clone(), "applied": self.actions.clone()}
+        if self._norm is not None and self._norm.ret is not None:
+            st["ret"] = self._norm.ret.clone()
         return st
 
     def set_state(self, qpos, qvel, qacc_warmstart=None, elapsed=None, episode=None, ee_joint_target=None,
-                  actuation=None):
+                  actuation=None, ret=None):
         """action_mode="ee_delta": ee_joint_target [N,5] restores the commanded joint targets (from ``get_state``);
         without it every command starts again from the new qpos.  ValueError in joint mode.  With the actuation model,
         actuation (``get_state()["actuation"]``: the command ring, head, act_params and the applied action) restores the
@@ -809,6 +929,10 @@ class SO100VecEnv:
             raise ValueError("ee_joint_target needs action_mode='ee_delta'")
         if actuation is not None and not self._act:
             raise ValueError("actuation state needs domain_randomization['actuation']")
+        if ret is not None:                          # normalize: the discounted returns (``get_state()["ret"]``)
+            if self._norm is None or self._norm.ret is None:
+                raise ValueError("ret needs normalize=... with a discount gamma")
+            self._norm.ret.copy_(torch.as_tensor(ret, dtype=torch.float64))
         if self._routed:
             if ee_joint_target is not None:
                 self.ee_joint_target.copy_(torch.as_tensor(ee_joint_target, dtype=torch.float32))

@@ -500,6 +500,80 @@ int so100_actuate(so100_env* env, const float* qpos /* [N,13] */, const float* c
                   float* hist /* [8][N][6] in/out */, int32_t* head /* [N] in/out */, float* action /* [N,6] in/out */,
                   void* stream);
 
+/* ---- (additions to ABI 25) running observation / reward normalisation on the device: SB3
+ * VecNormalize's running statistics in float64, as launches beside the untouched step.  Statistics of one normaliser:
+ * device double [3][SO100_NORM_MAX_DIM], row 0 the mean, row 1 the variance, row 2 the count of each column (they start
+ * at 0, 1 and 1e-4; the caller writes them).  A call names up to SO100_NORM_MAX_SRC sources, each rows of float32 at
+ * (x, row stride in floats, first column, dim); their columns, in order, are the statistics' columns 0 .. D-1,
+ * D = sum of dim <= SO100_NORM_MAX_DIM.
+ *   update, with the b rows whose mask byte is non-zero (mask NULL = all n; b = 0 changes nothing, bit for bit):
+ *     bm = batch mean, bv = population variance of the batch, delta = bm - mean, tot = count + b;
+ *     mean <- mean + delta b / tot;  var <- (var count + bv b + delta^2 count b / tot) / tot;  count <- tot.
+ *   The moments are float64 sums of (x - mean) and (x - mean)^2 per workgroup, a workgroup taking a contiguous range of
+ *   max(rows_per_group, ceil(n / max_groups)) rows (so100_norm_limits); the workgroups' partials are combined in
+ *   index order by a second launch, so the result is bit for bit reproducible.  No atomics on the statistics.
+ *   apply: y = clip((x - mean) / sqrt(var + epsilon), -clip, clip), computed in float64 and rounded once to float32, to
+ *     (y, y_stride) columns 0 .. dim-1 of each source; with a mask only the masked rows are written.  With
+ *     SO100_NORM_INVERSE in flags: y = x sqrt(var + epsilon) + mean (no clip).
+ * Workspace: so100_norm_work_bytes(n) = groups(n) * 3 * SO100_NORM_MAX_DIM * 8 bytes of device memory, groups(n) =
+ * min(max_groups, max(1, ceil(n / rows_per_group))); its contents carry nothing between calls. */
+#define SO100_NORM_MAX_DIM 32
+#define SO100_NORM_MAX_SRC 3
+#define SO100_NORM_INVERSE 1u
+typedef struct so100_norm_src {
+  const float* x;       /* device rows of float32 */
+  float*  y;            /* so100_norm_apply's output rows (may be x's own memory); so100_norm_update ignores it */
+  int32_t stride;       /* floats between rows of x, >= offset + dim */
+  int32_t offset;       /* first column read, >= 0 */
+  int32_t dim;          /* columns, >= 1 */
+  int32_t y_stride;     /* floats between rows of y, >= dim (apply only) */
+} so100_norm_src;
+typedef struct so100_norm {
+  uint32_t size;        /* sizeof(so100_norm): the callee rejects a mismatch */
+  int32_t  nsrc;        /* 1..SO100_NORM_MAX_SRC */
+  double   epsilon;     /* finite, > 0 */
+  double   clip;        /* finite, > 0 */
+  uint32_t flags;       /* SO100_NORM_INVERSE or 0 */
+  uint32_t reserved0;
+  so100_norm_src src[SO100_NORM_MAX_SRC];
+} so100_norm;
+int so100_norm_bytes(void);
+/* The moments kernel's constants: rows a workgroup takes below the grid cap, and the cap. */
+int so100_norm_limits(int* rows_per_group, int* max_groups);
+/* Bytes of workspace for n rows (the formula above); -1 for n < 0. */
+int so100_norm_work_bytes(int n);
+/* Both: launches on `stream` (update two, apply one), no allocation, no synchronisation; n = 0 launches nothing.
+ * Nonzero (text in so100_last_error) before any device work and with nothing written: NULL norm, a wrong `size`
+ * (checked first), nsrc outside 1..SO100_NORM_MAX_SRC, a dim outside 1..SO100_NORM_MAX_DIM, an offset < 0, a stride <
+ * offset + dim, a y_stride < dim (apply), a total dim > SO100_NORM_MAX_DIM, an epsilon or clip that is not finite or not
+ * positive, flags other than SO100_NORM_INVERSE, n < 0, a NULL env, a NULL source pointer x, a NULL y (apply), NULL
+ * stats, NULL work (update). */
+int so100_norm_update(so100_env* env, const so100_norm* norm, int n, const uint8_t* mask /* [n] or NULL */,
+                      double* stats /* [3][32] in/out */, void* work, void* stream);
+int so100_norm_apply(so100_env* env, const so100_norm* norm, int n, const uint8_t* mask /* [n] or NULL */,
+                     const double* stats /* [3][32] */, void* stream);
+/* The return path of reward normalisation, per env i, ret float64 [n], stats the one-column statistics of ret:
+ *   SO100_NORM_RET_UPDATE:    ret[i] <- ret[i] gamma + reward[i], then the update above with the n values of ret;
+ *   SO100_NORM_RET_NORMALIZE: reward_norm[i] = clip(reward[i] / sqrt(var + epsilon), -clip, clip)   (the updated var);
+ *   always:                   ret[i] <- 0 where terminated[i] or truncated[i] is non-zero (either may be NULL).
+ * Three launches (one without UPDATE) on `stream`, no allocation, no synchronisation.  Nonzero as above: NULL args, a
+ * wrong `size` (checked first), gamma outside (0, 1], a bad epsilon or clip, unknown flags, n < 0, a NULL env, reward,
+ * ret or stats, NULL work with UPDATE, NULL reward_norm with NORMALIZE. */
+#define SO100_NORM_RET_UPDATE 1u
+#define SO100_NORM_RET_NORMALIZE 2u
+typedef struct so100_norm_ret {
+  uint32_t size;        /* sizeof(so100_norm_ret): the callee rejects a mismatch */
+  uint32_t flags;
+  double   gamma;       /* in (0, 1] */
+  double   epsilon;     /* finite, > 0 */
+  double   clip;        /* finite, > 0 */
+} so100_norm_ret;
+int so100_norm_ret_bytes(void);
+int so100_norm_return(so100_env* env, const so100_norm_ret* args, int n, const float* reward /* [n] */,
+                      const uint8_t* terminated /* [n] or NULL */, const uint8_t* truncated /* [n] or NULL */,
+                      double* ret /* [n] in/out */, double* stats /* [3][32] in/out */, void* work,
+                      float* reward_norm /* [n] or NULL */, void* stream);
+
 /* Batched sparse GoalEnv reward (env.py:341-353): out[i] = ||a_i - d_i|| < threshold ? 0 : -1. */
 int so100_goal_reward(so100_env* env, int n, const float* achieved, const float* desired, float* out,
                       void* stream);
