@@ -71,6 +71,12 @@ hipError_t launch_norm_update(const so100_norm&, int, const uint8_t*, double*, d
 hipError_t launch_norm_apply(const so100_norm&, int, const uint8_t*, const double*, hipStream_t);
 hipError_t launch_norm_return(const so100_norm_ret&, int, const float*, const uint8_t*, const uint8_t*, double*, double*,
                               double*, float*, hipStream_t);
+int her_scan_group();
+int her_scan_tile();
+hipError_t launch_her_push(const so100_her&, const so100_her_step&, hipStream_t);
+hipError_t launch_her_discard(const so100_her&, const uint8_t*, const float*, const float*, hipStream_t);
+hipError_t launch_her_scan(const so100_her&, hipStream_t);
+hipError_t launch_her_sample(const DevModel*, const so100_her&, const so100_her_out&, int, int, uint64_t, hipStream_t);
 }  // namespace so100
 
 using so100::DevModel;
@@ -1696,6 +1702,91 @@ static int so100_norm_apply_impl(so100_env* env, const so100_norm* nm, int n, co
   return e == hipSuccess ? 0 : fail_hip("so100_norm_apply", e);
 }
 
+// the checks every so100_her_* call shares (include/so100.h): the record's numbers first, then (her_check_ptrs, after the
+// call's own records) the env and the arrays
+static int her_fail(const char* fn, const char* what) {
+  char msg[160];
+  snprintf(msg, sizeof(msg), "%s: %s", fn, what);
+  return fail(msg);
+}
+static int her_check(const char* fn, const so100_her* h, bool sample) {
+  if (!h) return her_fail(fn, "NULL her");
+  if (h->size != sizeof(so100_her)) return size_mismatch(fn, "so100_her", h->size, sizeof(so100_her));
+  if (h->T < 1) return her_fail(fn, "T < 1");
+  if (h->n < 0) return her_fail(fn, "n < 0");
+  if ((long long)h->T * h->n >= (1ll << 31)) return her_fail(fn, "T * n >= 2^31");
+  if (h->action_dim < 1 || h->action_dim > SO100_HER_MAX_ACTION) return her_fail(fn, "action_dim outside 1..16");
+  if (sample) {
+    if (h->strategy != SO100_HER_FUTURE && h->strategy != SO100_HER_FINAL && h->strategy != SO100_HER_EPISODE)
+      return her_fail(fn, "unknown strategy");
+    if (h->n_sampled_goal < 0) return her_fail(fn, "n_sampled_goal < 0");
+  }
+  return 0;
+}
+static int her_check_ptrs(const char* fn, const so100_env* env, const so100_her* h) {
+  if (!env) return her_fail(fn, "NULL env");
+  if (!h->obs || !h->next_obs || !h->goal || !h->action || !h->reward || !h->terminated || !h->offset || !h->length ||
+      !h->meta || !h->stage_obs || !h->stage_goal || !h->prefix)
+    return her_fail(fn, "NULL array in so100_her");
+  return 0;
+}
+
+static int so100_her_push_impl(so100_env* env, const so100_her* h, const so100_her_step* st, void* stream) {
+  const char* fn = "so100_her_push";
+  if (int rc = her_check(fn, h, false)) return rc;
+  if (!st) return her_fail(fn, "NULL step");
+  if (st->size != sizeof(so100_her_step)) return size_mismatch(fn, "so100_her_step", st->size, sizeof(so100_her_step));
+  if (int rc = her_check_ptrs(fn, env, h)) return rc;
+  if (!st->prev_obs || !st->prev_goal || !st->obs || !st->final_obs || !st->goal || !st->action || !st->reward ||
+      !st->terminated || !st->truncated)
+    return her_fail(fn, "NULL pointer in so100_her_step");
+  if (h->n == 0) return 0;
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_her_push(*h, *st, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip(fn, e);
+}
+
+static int so100_her_discard_impl(so100_env* env, const so100_her* h, const uint8_t* mask, const float* obs,
+                                  const float* goal, void* stream) {
+  const char* fn = "so100_her_discard";
+  if (int rc = her_check(fn, h, false)) return rc;
+  if (int rc = her_check_ptrs(fn, env, h)) return rc;
+  if (h->n == 0) return 0;
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_her_discard(*h, mask, obs, goal, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip(fn, e);
+}
+
+static int so100_her_scan_impl(so100_env* env, const so100_her* h, void* stream) {
+  const char* fn = "so100_her_scan";
+  if (int rc = her_check(fn, h, false)) return rc;
+  if (int rc = her_check_ptrs(fn, env, h)) return rc;
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_her_scan(*h, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip(fn, e);
+}
+
+static int so100_her_sample_impl(so100_env* env, const so100_her* h, int batch, uint64_t call, const so100_her_out* o,
+                                 void* stream) {
+  const char* fn = "so100_her_sample";
+  if (int rc = her_check(fn, h, true)) return rc;
+  if (batch < 0) return her_fail(fn, "batch < 0");
+  if (!o) return her_fail(fn, "NULL out");
+  if (o->size != sizeof(so100_her_out)) return size_mismatch(fn, "so100_her_out", o->size, sizeof(so100_her_out));
+  if (int rc = her_check_ptrs(fn, env, h)) return rc;
+  if (!o->observation || !o->achieved_goal || !o->desired_goal || !o->next_observation || !o->next_achieved_goal ||
+      !o->next_desired_goal || !o->actions || !o->rewards || !o->dones || !o->env || !o->slot || !o->goal_slot)
+    return her_fail(fn, "NULL pointer in so100_her_out");
+  if (batch == 0) return 0;
+  // the relabelled rows: int(her_ratio * batch), her_ratio = 1 - 1 / (n_sampled_goal + 1), in float64 as SB3 computes it
+  const double ratio = 1.0 - 1.0 / ((double)h->n_sampled_goal + 1.0);
+  int nrel = (int)(ratio * (double)batch);
+  nrel = nrel < 0 ? 0 : (nrel > batch ? batch : nrel);
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_her_sample(env->d_model, *h, *o, batch, nrel, call, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip(fn, e);
+}
+
 static int so100_norm_return_impl(so100_env* env, const so100_norm_ret* a, int n, const float* reward,
                                   const uint8_t* terminated, const uint8_t* truncated, double* ret, double* stats,
                                   void* work, float* reward_norm, void* stream) {
@@ -1766,6 +1857,60 @@ int so100_actuate(so100_env* env, const float* qpos, const float* command, const
     return so100_actuate_impl(env, qpos, command, reinit, act_params, hist, head, action, stream);
   } catch (...) {
     return caught("so100_actuate");
+  }
+}
+
+int so100_her_bytes(void) { return (int)sizeof(so100_her); }
+int so100_her_step_bytes(void) { return (int)sizeof(so100_her_step); }
+int so100_her_out_bytes(void) { return (int)sizeof(so100_her_out); }
+
+int so100_her_limits(int* scan_group, int* scan_tile) {
+  if (!scan_group || !scan_tile) return fail("so100_her_limits: NULL argument");
+  *scan_group = so100::her_scan_group();
+  *scan_tile = so100::her_scan_tile();
+  return 0;
+}
+
+int64_t so100_her_storage_bytes(int n, int T, int action_dim) {
+  if (n < 0 || T < 1 || (long long)T * n >= (1ll << 31) || action_dim < 1 || action_dim > SO100_HER_MAX_ACTION) {
+    fail("so100_her_storage_bytes: n < 0, T < 1, T * n >= 2^31 or action_dim outside 1..16");
+    return -1;
+  }
+  const int64_t slots = (int64_t)T * n;
+  return slots * (4 * (SO100_NOBS + SO100_NOBS + 3 + action_dim + 1 + 2) + 1) + 4 * (3 * (int64_t)n + 18 * (int64_t)n + n + 1);
+}
+
+int so100_her_push(so100_env* env, const so100_her* her, const so100_her_step* step, void* stream) {
+  try {
+    return so100_her_push_impl(env, her, step, stream);
+  } catch (...) {
+    return caught("so100_her_push");
+  }
+}
+
+int so100_her_discard(so100_env* env, const so100_her* her, const uint8_t* mask, const float* obs, const float* goal,
+                      void* stream) {
+  try {
+    return so100_her_discard_impl(env, her, mask, obs, goal, stream);
+  } catch (...) {
+    return caught("so100_her_discard");
+  }
+}
+
+int so100_her_scan(so100_env* env, const so100_her* her, void* stream) {
+  try {
+    return so100_her_scan_impl(env, her, stream);
+  } catch (...) {
+    return caught("so100_her_scan");
+  }
+}
+
+int so100_her_sample(so100_env* env, const so100_her* her, int batch, uint64_t call, const so100_her_out* out,
+                     void* stream) {
+  try {
+    return so100_her_sample_impl(env, her, batch, call, out, stream);
+  } catch (...) {
+    return caught("so100_her_sample");
   }
 }
 

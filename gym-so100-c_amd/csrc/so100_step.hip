@@ -24,6 +24,7 @@
 #include "so100_newton.h"
 #include "so100_dynamics.h"
 #include "so100_task.h"
+#include "so100_goal.h"
 #include "so100_boxbox.h"
 #include "so100_convex.h"
 #include "so100_rows.h"
@@ -1346,10 +1347,8 @@ __global__ void so100_unnormalize_kernel(const DevModel* m, int n, const float* 
 __global__ void so100_goal_reward_kernel(const DevModel* m, int n, const float* a, const float* d, float* out) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  // np.linalg.norm(achieved - desired, axis=1) in float32 (env.py:347-349)
-  float d0 = a[3 * i] - d[3 * i], d1 = a[3 * i + 1] - d[3 * i + 1], d2 = a[3 * i + 2] - d[3 * i + 2];
-  float dist = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
-  out[i] = dist < (float)m->goal_threshold ? 0.f : -1.f;
+  out[i] = goal_reward_f32(a[3 * i], a[3 * i + 1], a[3 * i + 2], d[3 * i], d[3 * i + 1], d[3 * i + 2],
+                           (float)m->goal_threshold);
 }
 
 // ------------------------------------------------------------------ launchers (called by so100_capi.cpp)

@@ -200,6 +200,62 @@ class SO100NormRet(ctypes.Structure):
         self.gamma, self.epsilon, self.clip = float(gamma), float(epsilon), float(clip)
 
 
+SO100_HER_FUTURE, SO100_HER_FINAL, SO100_HER_EPISODE = 0, 1, 2     # include/so100.h: so100_her.strategy
+SO100_HER_MAX_ACTION = 16
+HER_STRATEGIES = {"future": SO100_HER_FUTURE, "final": SO100_HER_FINAL, "episode": SO100_HER_EPISODE}
+HER_ARRAYS = ("obs", "next_obs", "goal", "action", "reward", "terminated", "offset", "length", "meta", "stage_obs",
+              "stage_goal", "prefix")
+HER_STEP_INPUTS = ("prev_obs", "prev_goal", "obs", "final_obs", "goal", "action", "reward", "terminated", "truncated",
+                   "diverged", "discard")
+HER_OUTPUTS = ("observation", "achieved_goal", "desired_goal", "next_observation", "next_achieved_goal",
+               "next_desired_goal", "actions", "rewards", "dones", "env", "slot", "goal_slot")
+
+
+class SO100Her(ctypes.Structure):
+    """Mirror of ``so100_her`` (include/so100.h): the shape, the sampling options and the device arrays of one hindsight
+    replay buffer.  ``size`` is set to the mirror's size, which the callee checks against its own."""
+    _fields_ = [("size", ctypes.c_uint32), ("n", ctypes.c_int32), ("T", ctypes.c_int32), ("action_dim", ctypes.c_int32),
+                ("strategy", ctypes.c_int32), ("n_sampled_goal", ctypes.c_int32), ("seed", ctypes.c_uint64)] + \
+               [(name, _P) for name in HER_ARRAYS]
+
+    def __init__(self, n=0, T=1, action_dim=6, strategy=SO100_HER_FUTURE, n_sampled_goal=4, seed=0, **arrays):
+        super().__init__()
+        self.size = ctypes.sizeof(SO100Her)
+        self.n, self.T, self.action_dim = int(n), int(T), int(action_dim)
+        self.strategy, self.n_sampled_goal = int(strategy), int(n_sampled_goal)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        for name, p in arrays.items():
+            if name not in HER_ARRAYS:
+                raise TypeError(f"so100_her has no array {name!r}")
+            setattr(self, name, p)
+
+
+class SO100HerStep(ctypes.Structure):
+    """Mirror of ``so100_her_step`` (include/so100.h): the device rows one ``so100_her_push`` reads."""
+    _fields_ = [("size", ctypes.c_uint32), ("reserved0", ctypes.c_uint32)] + [(name, _P) for name in HER_STEP_INPUTS]
+
+    def __init__(self, **inputs):
+        super().__init__()
+        self.size = ctypes.sizeof(SO100HerStep)
+        for name, p in inputs.items():
+            if name not in HER_STEP_INPUTS:
+                raise TypeError(f"so100_her_step has no input {name!r}")
+            setattr(self, name, p)
+
+
+class SO100HerOut(ctypes.Structure):
+    """Mirror of ``so100_her_out`` (include/so100.h): the device arrays one ``so100_her_sample`` fills."""
+    _fields_ = [("size", ctypes.c_uint32), ("reserved0", ctypes.c_uint32)] + [(name, _P) for name in HER_OUTPUTS]
+
+    def __init__(self, **outputs):
+        super().__init__()
+        self.size = ctypes.sizeof(SO100HerOut)
+        for name, p in outputs.items():
+            if name not in HER_OUTPUTS:
+                raise TypeError(f"so100_her_out has no output {name!r}")
+            setattr(self, name, p)
+
+
 SO100_NMATERIAL = 5
 
 
@@ -317,6 +373,17 @@ def load():
     lib.so100_norm_update.argtypes = [_P, ctypes.POINTER(SO100Norm), ctypes.c_int, _P, _P, _P, _P]
     lib.so100_norm_apply.argtypes = [_P, ctypes.POINTER(SO100Norm), ctypes.c_int, _P, _P, _P]
     lib.so100_norm_return.argtypes = [_P, ctypes.POINTER(SO100NormRet), ctypes.c_int, _P, _P, _P, _P, _P, _P, _P, _P]
+    lib.so100_her_bytes.argtypes = []
+    lib.so100_her_step_bytes.argtypes = []
+    lib.so100_her_out_bytes.argtypes = []
+    lib.so100_her_limits.argtypes = [_P, _P]
+    lib.so100_her_storage_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    lib.so100_her_storage_bytes.restype = ctypes.c_int64
+    lib.so100_her_push.argtypes = [_P, ctypes.POINTER(SO100Her), ctypes.POINTER(SO100HerStep), _P]
+    lib.so100_her_discard.argtypes = [_P, ctypes.POINTER(SO100Her), _P, _P, _P, _P]
+    lib.so100_her_scan.argtypes = [_P, ctypes.POINTER(SO100Her), _P]
+    lib.so100_her_sample.argtypes = [_P, ctypes.POINTER(SO100Her), ctypes.c_int, ctypes.c_uint64,
+                                     ctypes.POINTER(SO100HerOut), _P]
     lib.so100_hull_cells.argtypes = [_P, _P, _P, ctypes.c_int]
     lib.so100_hull_blocks.argtypes = [_P, _P, ctypes.c_int]
     lib.so100_hull_support_probe.argtypes = [_P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P]
@@ -339,7 +406,9 @@ def load():
                "so100_ee_ctrl_bytes", "so100_ee_action", "so100_ee_jacobian", "so100_hull_blocks",
                "so100_hull_support_probe", "so100_dr_ranges_bytes", "so100_dr_sample", "so100_actuate",
                "so100_norm_bytes", "so100_norm_ret_bytes", "so100_norm_limits", "so100_norm_work_bytes",
-               "so100_norm_update", "so100_norm_apply", "so100_norm_return"):
+               "so100_norm_update", "so100_norm_apply", "so100_norm_return", "so100_her_bytes",
+               "so100_her_step_bytes", "so100_her_out_bytes", "so100_her_limits", "so100_her_push",
+               "so100_her_discard", "so100_her_scan", "so100_her_sample"):
         getattr(lib, fn).restype = ctypes.c_int
     lib.so100_struct_sizes.argtypes = [_P, _P]
     lib.so100_struct_sizes.restype = ctypes.c_int
@@ -376,6 +445,10 @@ def load():
         raise NativeLibraryError(f"struct layout mismatch: so100_norm {lib.so100_norm_bytes()} vs "
                                  f"{ctypes.sizeof(SO100Norm)}, so100_norm_ret {lib.so100_norm_ret_bytes()} vs "
                                  f"{ctypes.sizeof(SO100NormRet)}")
+    for fn, mirror in (("so100_her_bytes", SO100Her), ("so100_her_step_bytes", SO100HerStep),
+                       ("so100_her_out_bytes", SO100HerOut)):
+        if getattr(lib, fn)() != ctypes.sizeof(mirror):
+            raise NativeLibraryError(f"struct layout mismatch: {fn} {getattr(lib, fn)()} vs {ctypes.sizeof(mirror)}")
     _lib = lib
     return lib
 
@@ -385,6 +458,13 @@ def norm_limits():
     r, g = ctypes.c_int(0), ctypes.c_int(0)
     check(load().so100_norm_limits(ctypes.byref(r), ctypes.byref(g)), "so100_norm_limits")
     return r.value, g.value
+
+
+def her_limits():
+    """(the scan's workgroup size, the elements one pass of it takes) (so100_her_limits)."""
+    w, t = ctypes.c_int(0), ctypes.c_int(0)
+    check(load().so100_her_limits(ctypes.byref(w), ctypes.byref(t)), "so100_her_limits")
+    return w.value, t.value
 
 
 EXPORTED_SYMBOLS = ("so100_abi_version", "so100_last_error", "so100_source_hash", "so100_struct_sizes", "so100_create", "so100_destroy", "so100_num_envs",
@@ -401,7 +481,9 @@ EXPORTED_SYMBOLS = ("so100_abi_version", "so100_last_error", "so100_source_hash"
                     "so100_ee_ctrl_bytes", "so100_ee_action", "so100_ee_jacobian", "so100_hull_blocks",
                     "so100_hull_support_probe", "so100_dr_ranges_bytes", "so100_dr_sample", "so100_actuate",
                     "so100_norm_bytes", "so100_norm_ret_bytes", "so100_norm_limits", "so100_norm_work_bytes",
-                    "so100_norm_update", "so100_norm_apply", "so100_norm_return")
+                    "so100_norm_update", "so100_norm_apply", "so100_norm_return", "so100_her_bytes",
+                    "so100_her_step_bytes", "so100_her_out_bytes", "so100_her_limits", "so100_her_storage_bytes",
+                    "so100_her_push", "so100_her_discard", "so100_her_scan", "so100_her_sample")
 
 
 def source_hash():

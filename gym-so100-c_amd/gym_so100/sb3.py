@@ -53,11 +53,16 @@ on the device, and the adapter hands out the normalised obser
 (an ``.npz`` of the env's ``normalize_state()``; not SB3's pickle).  With pixel observations only ``agent_pos`` is
 normalised, and nothing more is copied to the host than without the option.
 
+``replay=dict(buffer_size=...)`` is forwarded to the env (GoalEnv, state observation): every ``step`` then stores its
+transitions in the device-resident hindsight buffer, and ``SO100HerReplayBuffer`` below hands it to an
+off-policy learner in ``HerReplayBuffer``'s place: ``add`` has nothing left to do, ``sample`` returns device tensors.
+
 The image (or flattened) tensor reaches the host by one asynchronous copy into pinned memory and one stream
 synchronisation per step.  Two pinned buffers alternate: **the image array of an observation returned by
 ``reset()`` / ``step()`` stays valid through the next ``step()`` and is overwritten by the one after it** (SB3's
 collectors hold ``_last_obs`` across one step); copy it to keep it longer.
 """
+import collections
 import time
 
 import numpy as np
@@ -69,6 +74,10 @@ try:  # optional dependency (absent in this image)
     from stable_baselines3.common.vec_env.base_vec_env import VecEnv as _VecEnvBase
 except ImportError:  # pragma: no cover - exercised when SB3 is installed
     _VecEnvBase = object
+try:
+    from stable_baselines3.common.buffers import ReplayBuffer as _ReplayBufferBase
+except ImportError:  # pragma: no cover
+    _ReplayBufferBase = object
 
 
 def _np(t):
@@ -83,7 +92,7 @@ class SO100SB3VecEnv(_VecEnvBase):
     def __init__(self, num_envs, task="so100_cube_to_bin", device="cuda:0", seed=0, max_episode_steps=None,
                  domain_randomization=None, env_offset=0, iterations=None, solver="newton", obs_type="so100_state",
                  observation_width=640, observation_height=480, channels_first=False, cameras=None, shadows=False,
-                 antialias=False, action_mode="joint", ee_control=None, normalize=None):
+                 antialias=False, action_mode="joint", ee_control=None, normalize=None, replay=None):
         self.pixel_obs = obs_type == "so100_pixels_agent_pos"
         kw = {}
         self._last_obs = None                      # the observation last returned (get_original_obs: its image)
@@ -114,6 +123,8 @@ class SO100SB3VecEnv(_VecEnvBase):
             kw["action_mode"], kw["ee_control"] = action_mode, ee_control
         if normalize is not None:                                  # the env's own checks (ValueError) apply
             kw["normalize"] = normalize
+        if replay is not None:                                     # the env's own checks (ValueError) apply
+            kw["replay"] = replay
         self.venv = SO100VecEnv(num_envs, task=task, device=device, seed=seed, max_episode_steps=max_episode_steps,
                                 autoreset=True, domain_randomization=domain_randomization, env_offset=env_offset,
                                 iterations=iterations, solver=solver, episode_stats=True, **kw)
@@ -408,3 +419,46 @@ class SO100SB3VecEnv(_VecEnvBase):
     @property
     def device(self):
         return self.venv.device
+
+
+# SB3's DictReplayBufferSamples, field for field (type_aliases.py); the values are device tensors
+HerReplaySamples = collections.namedtuple("HerReplaySamples",
+                                          ["observations", "actions", "next_observations", "dones", "rewards"])
+
+
+class SO100HerReplayBuffer(_ReplayBufferBase):
+    """The env's device-resident hindsight buffer (``SO100VecEnv(replay=...)``) behind the calls an
+    SB3 off-policy learner makes on ``HerReplayBuffer``: ``SAC(..., replay_buffer_class=SO100HerReplayBuffer,
+    replay_buffer_kwargs=dict(env=env))``.  The env has stored every transition by the time the learner calls ``add``, so
+    ``add`` does nothing; ``sample`` draws and relabels on the device and returns torch tensors there.  SB3's own storage
+    is never allocated (its ``__init__`` is not run)."""
+
+    def __init__(self, buffer_size=None, observation_space=None, action_space=None, env=None, device="auto", n_envs=None,
+                 **_ignored):
+        venv = getattr(env, "venv", env)
+        if venv is None or getattr(venv, "replay", None) is None:
+            raise ValueError("SO100HerReplayBuffer needs env=: an SO100SB3VecEnv / SO100VecEnv built with replay=...")
+        self.venv, self.replay = venv, venv.replay
+        self.buffer_size = self.replay.T                     # SB3 counts slots per env
+        self.n_envs = venv.num_envs
+        self.observation_space = observation_space if observation_space is not None else \
+            getattr(env, "observation_space", None)
+        self.action_space = action_space if action_space is not None else getattr(env, "action_space", None)
+        self.device = venv.device
+        self.pos, self.full = 0, False
+
+    def add(self, *args, **kwargs):
+        """nothing: ``step`` has already pushed this transition on the device"""
+
+    def size(self):
+        """the transitions a sample draws from (waits for the device)"""
+        return self.replay.size()
+
+    def sample(self, batch_size, env=None):
+        """observations / next_observations: dicts of [B, .] tensors (observation, achieved_goal, desired_goal), normalised
+        where the env was built with ``normalize=...``; actions [B, A]; dones and rewards [B, 1]."""
+        b = self.replay.sample(batch_size, normalize=self.venv._norm is not None)
+        keys = ("observation", "achieved_goal", "desired_goal")
+        return HerReplaySamples(observations={k: b[k] for k in keys}, actions=b["actions"],
+                                next_observations={k: b["next_" + k] for k in keys},
+                                dones=b["dones"].reshape(-1, 1), rewards=b["rewards"].reshape(-1, 1))

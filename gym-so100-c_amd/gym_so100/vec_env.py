@@ -34,6 +34,7 @@ from . import _native
 from .model import NOBS, NQ, NV, build_model
 from .constants import GOAL_MAX_EPISODE_STEPS
 from .normalize import Normalizer, merge_normalize_states, normalize_options  # noqa: F401  (re-exported)
+from .replay import HerReplay, replay_options
 
 _MAX_STEPS = {"so100_cube_to_bin": 700, "so100_touch_cube": 300, "so100_touch_cube_sparse": 300,
               "so100_goal": GOAL_MAX_EPISODE_STEPS}
@@ -272,6 +273,15 @@ class SO100VecEnv:
             they are.  ``training`` (settable), ``obs_rms``, ``ret_rms``, ``normalize_obs``, ``unnormalize_obs``,
             ``normalize_state`` and ``set_normalize_state`` below.  ValueError for unknown keys and bad values, and for
             the GoalEnv's flattened pixel observation (thousands of columns: not normalised).
+        replay: None (default: every call what it is without the argument, ``replay`` is None) or a dict overriding
+            replay.REPLAY_DEFAULTS (buffer_size, n_sampled_goal, goal_selection_strategy, seed): SB3
+            HerReplayBuffer's storage and hindsight relabelling, on the device (csrc/so100_her.hip, include/so100.h
+            so100_her_push; DESIGN.md §3.11).  ``buffer_size // num_envs`` slots per env; every ``step`` stores one
+            transition per env (the raw observation, the true next observation, the goal, the command as passed in, the
+            reward, ``terminated``) with no host synchronisation, ``reset`` drops the open episodes of the envs it
+            resets, a diverged episode is erased, and ``replay.sample(batch_size)`` draws from the finished episodes.
+            ``step_async_raw`` stores nothing.  ValueError for unknown keys and bad values, and unless
+            task="so100_goal", obs_type="so100_state", autoreset=True and buffer_size // num_envs >= max_episode_steps.
     """
 
     def __init__(self, num_envs, task="so100_cube_to_bin", obs_type="so100_state", device="cuda:0", seed=0,
@@ -279,9 +289,11 @@ class SO100VecEnv:
                  iterations=None, debug=False, solver="newton", observation_width=640, observation_height=480,
                  variant="joint", reward64=False, nsubstep=None, convex="epa", episode_stats=False, channels_first=False,
                  flat_pixels=False, depth=False, segmentation=False, cameras=None, shadows=False,
-                 antialias=False, action_mode="joint", ee_control=None, normalize=None):
+                 antialias=False, action_mode="joint", ee_control=None, normalize=None, replay=None):
         torch = _torch()
         norm_options = normalize_options(normalize)      # its ValueErrors before any device work
+        replay_opts = replay_options(replay, num_envs, task, obs_type, autoreset,
+                                     _MAX_STEPS.get(task) if max_episode_steps is None else max_episode_steps)
         if norm_options is not None and norm_options["obs"] and task == "so100_goal" \
                 and obs_type == "so100_pixels_agent_pos":
             raise ValueError("normalize: the GoalEnv's flattened pixel observation ([N, 3HW+6]) is not normalised; use "
@@ -460,6 +472,7 @@ class SO100VecEnv:
             self.final_obs_norm = self._norm.final_out      # [N,15], or the final agent_pos [N,6] with pixels
             self.reward_norm = self._norm.reward_norm
             self._pre = True
+        self.replay = None if replay_opts is None else HerReplay(self, replay_opts)
 
     # ------------------------------------------------------------------ plumbing
     def _fill_buffers(self):
@@ -646,6 +659,8 @@ class SO100VecEnv:
             self._render_all()
         if self._norm is not None:                       # the reset envs' observations enter the statistics
             self._norm.after_reset(None if mask is None else self._mask)
+        if self.replay is not None:                      # the reset envs' open episodes go, their fresh rows are staged
+            self.replay.after_reset(None if mask is None else self._mask)
         info = {"is_success": torch.zeros_like(self.success)}
         return self._observation(), info
 
@@ -684,6 +699,8 @@ class SO100VecEnv:
             self._epilogue()
         if self._norm is not None:
             self._norm.after_step()
+        if self.replay is not None:                      # one transition per env, with the command as it came in
+            self.replay.after_step(dst)
         info = {"is_success": self.success, "diverged": self.diverged, "contact_bits": self.contact_bits,
                 "ncon_dropped": self.ncon_dropped}
         if self.autoreset:

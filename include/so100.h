@@ -574,6 +574,132 @@ int so100_norm_return(so100_env* env, const so100_norm_ret* args, int n, const f
                       double* ret /* [n] in/out */, double* stats /* [3][32] in/out */, void* work,
                       float* reward_norm /* [n] or NULL */, void* stream);
 
+/* ---- (additions to ABI 25) a hindsight replay buffer for the GoalEnv on the device: SB3's
+ * HerReplayBuffer (scripts/train_sac_her.py:236-251 trains with n_sampled_goal = 4, "future") as launches beside the
+ * untouched step.  The caller owns every array; so100_her names them.
+ *
+ * Storage.  A ring of T slots for each of n envs, slot-major ([T][n][...]: the envs of one slot are contiguous, so a push
+ * writes contiguous rows).  Slot s of env e holds one transition: obs (the raw observation before the step), next_obs
+ * (the true next observation: the final_obs row where the env finished, else the new obs row), goal (the desired goal in
+ * force during the step), action (the command given to step), reward, terminated, offset (the transition's index within
+ * its episode) and, at an episode's first slot once the episode has closed, length (the episode's transitions).  The
+ * achieved goal and the next achieved goal are columns 0..2 of obs and next_obs.  An episode's first slot is
+ * (s - offset) mod T, so its length is one load away from any of its slots.
+ * Metadata, int32 meta[3][n]: valid_lo[e], count[e], open_len[e].  The count[e] transitions of closed, intact episodes
+ * occupy the slots valid_lo, valid_lo + 1, .. (mod T) in episode order; the open episode's open_len[e] transitions follow
+ * them; the write cursor is (valid_lo + count + open_len) mod T.  count + open_len <= T.  All zero at the start.
+ *
+ * so100_her_push, env e (one launch):
+ *   1. count + open_len == T (the ring is full): with count > 0 the oldest closed episode goes whole, L = length[valid_lo]:
+ *      valid_lo <- (valid_lo + L) mod T, count <- count - L; with count == 0 (an open episode of T transitions: a caller
+ *      with T >= its episode cap never gets here) the open episode goes, open_len <- 0.
+ *   2. the transition is written at the cursor with offset = open_len (obs and goal from prev_obs / prev_goal);
+ *      open_len <- open_len + 1.
+ *   3. diverged[e] or discard[e] non-zero: the open episode, this transition included, is erased: open_len <- 0 (the
+ *      cursor moves back over it: no hole).  Else terminated[e] | truncated[e]: the episode closes: length[first slot]
+ *      <- open_len, count <- count + open_len, open_len <- 0.
+ *   4. stage_obs[e] <- obs[e], stage_goal[e] <- goal[e]: the next transition's "before" values.  stage_obs / stage_goal
+ *      may be prev_obs / prev_goal themselves (each element is read before it is written, by the same thread).
+ * so100_her_discard: open_len <- 0 for the envs whose mask byte is non-zero (mask NULL = all), and, where obs / goal are
+ *   given, stage_obs / stage_goal <- their rows for the same envs (after a reset).
+ * so100_her_scan (one launch, one workgroup): prefix[e] = count[0] + .. + count[e] for e < n, prefix[n] = the total.
+ * so100_her_sample, batch element i (one launch; it reads prefix, so a scan must follow the last push), with
+ *   draw(field) = splitmix64(splitmix64(seed ^ (i * 0x100000001B3) ^ (field * 0xD1B54A32D192ED03)) + call), all in
+ *   uint64 arithmetic mod 2^64, splitmix64 the finaliser of so100_views_sample (x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30)
+ *   * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31), and `call` the caller's count of sample
+ *   calls:
+ *   total = prefix[n]; total == 0: every output row i is 0, env[i] = 0, slot[i] = goal_slot[i] = -1, nothing of the ring
+ *     is read.  Else
+ *   r = floor(draw(0) * total / 2^64); e = the first env with prefix[e] > r; slot = (valid_lo[e] + r - prefix[e-1]) mod T
+ *     (prefix[-1] = 0): every valid transition is equally likely;
+ *   o = offset[slot], first = (slot - o) mod T, len = length[first];
+ *   i < floor((1 - 1 / (n_sampled_goal + 1)) * batch) (in float64): the row is relabelled, with the transition
+ *     j = o + floor(draw(1) * (len - o) / 2^64) (SO100_HER_FUTURE: the transition's own next achieved goal included),
+ *     j = len - 1 (SO100_HER_FINAL) or j = floor(draw(1) * len / 2^64) (SO100_HER_EPISODE) of the same episode:
+ *     goal_slot = (first + j) mod T, desired_goal = next_obs[goal_slot][0:3], reward = so100_goal_reward(next_obs[slot]
+ *     [0:3], desired_goal) (the same device function); the other rows keep their stored goal and reward, goal_slot = -1;
+ *   gathered: observation, achieved_goal (= observation[0:3]), desired_goal, next_observation, next_achieved_goal,
+ *     next_desired_goal (= desired_goal), actions, rewards, dones (the stored terminated as 0 / 1: SB3's dones *
+ *     (1 - timeouts)), env, slot, goal_slot.
+ * Every index read from meta, offset, length or prefix is clamped into its range before it addresses memory. */
+#define SO100_HER_FUTURE 0
+#define SO100_HER_FINAL 1
+#define SO100_HER_EPISODE 2
+#define SO100_HER_MAX_ACTION 16
+typedef struct so100_her {
+  uint32_t size;            /* sizeof(so100_her): the callee rejects a mismatch */
+  int32_t  n;               /* envs, >= 0 */
+  int32_t  T;               /* slots per env, >= 1, T * n < 2^31 */
+  int32_t  action_dim;      /* floats per command, 1..SO100_HER_MAX_ACTION */
+  int32_t  strategy;        /* SO100_HER_FUTURE | _FINAL | _EPISODE (sample) */
+  int32_t  n_sampled_goal;  /* >= 0 (sample) */
+  uint64_t seed;            /* (sample) */
+  float*   obs;             /* [T][n][15] */
+  float*   next_obs;        /* [T][n][15] */
+  float*   goal;            /* [T][n][3] */
+  float*   action;          /* [T][n][action_dim] */
+  float*   reward;          /* [T][n] */
+  uint8_t* terminated;      /* [T][n] */
+  int32_t* offset;          /* [T][n] */
+  int32_t* length;          /* [T][n] */
+  int32_t* meta;            /* [3][n]: valid_lo, count, open_len */
+  float*   stage_obs;       /* [n][15] */
+  float*   stage_goal;      /* [n][3] */
+  int32_t* prefix;          /* [n + 1] */
+} so100_her;
+int so100_her_bytes(void);
+/* The inputs of one push: device rows of the n envs, as the step left them. */
+typedef struct so100_her_step {
+  uint32_t size;              /* sizeof(so100_her_step) */
+  uint32_t reserved0;
+  const float*   prev_obs;    /* [n][15]: the observation before the step (the staged rows) */
+  const float*   prev_goal;   /* [n][3]: the desired goal in force during the step */
+  const float*   obs;         /* [n][15] */
+  const float*   final_obs;   /* [n][15]: read where terminated | truncated */
+  const float*   goal;        /* [n][3]: the desired goal after the step (a finished env's new one) */
+  const float*   action;      /* [n][action_dim] */
+  const float*   reward;      /* [n] */
+  const uint8_t* terminated;  /* [n] */
+  const uint8_t* truncated;   /* [n] */
+  const uint8_t* diverged;    /* [n] or NULL */
+  const uint8_t* discard;     /* [n] or NULL */
+} so100_her_step;
+int so100_her_step_bytes(void);
+/* The outputs of one sample call: device arrays of `batch` rows, every one required. */
+typedef struct so100_her_out {
+  uint32_t size;              /* sizeof(so100_her_out) */
+  uint32_t reserved0;
+  float* observation;         /* [B][15] */
+  float* achieved_goal;       /* [B][3] */
+  float* desired_goal;        /* [B][3] */
+  float* next_observation;    /* [B][15] */
+  float* next_achieved_goal;  /* [B][3] */
+  float* next_desired_goal;   /* [B][3] */
+  float* actions;             /* [B][action_dim] */
+  float* rewards;             /* [B] */
+  float* dones;               /* [B] */
+  int32_t* env;               /* [B] */
+  int32_t* slot;              /* [B] */
+  int32_t* goal_slot;         /* [B] */
+} so100_her_out;
+int so100_her_out_bytes(void);
+/* The scan's workgroup size W and the elements one pass of the workgroup takes (a multiple of W). */
+int so100_her_limits(int* scan_group, int* scan_tile);
+/* Bytes of all the arrays of so100_her together: T n (4 (15 + 15 + 3 + action_dim + 1 + 2) + 1) + 4 (3 n + 18 n + n + 1);
+ * -1 (text in so100_last_error) for n < 0, T < 1, T * n >= 2^31 or an action_dim outside 1..SO100_HER_MAX_ACTION. */
+int64_t so100_her_storage_bytes(int n, int T, int action_dim);
+/* All four: launches on `stream` (one each), no allocation, no synchronisation, no atomics; push and discard launch nothing
+ * for n = 0, sample nothing for batch = 0.  Nonzero (text in so100_last_error) before any device work and with nothing written, in this order:
+ * NULL her, a wrong `size`, T < 1, n < 0, T * n >= 2^31, an action_dim outside 1..SO100_HER_MAX_ACTION, (sample) an
+ * unknown strategy, n_sampled_goal < 0, batch < 0, NULL out or a wrong `size` of it, (push) NULL step or a wrong `size` of
+ * it; then a NULL env, a NULL array of so100_her, a NULL required pointer of step or out. */
+int so100_her_push(so100_env* env, const so100_her* her, const so100_her_step* step, void* stream);
+int so100_her_discard(so100_env* env, const so100_her* her, const uint8_t* mask /* [n] or NULL */,
+                      const float* obs /* [n][15] or NULL */, const float* goal /* [n][3] or NULL */, void* stream);
+int so100_her_scan(so100_env* env, const so100_her* her, void* stream);
+int so100_her_sample(so100_env* env, const so100_her* her, int batch, uint64_t call, const so100_her_out* out,
+                     void* stream);
+
 /* Batched sparse GoalEnv reward (env.py:341-353): out[i] = ||a_i - d_i|| < threshold ? 0 : -1. */
 int so100_goal_reward(so100_env* env, int n, const float* achieved, const float* desired, float* out,
                       void* stream);
