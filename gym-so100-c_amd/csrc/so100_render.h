@@ -483,8 +483,16 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
         atomicMin(&zd[(y - y0) * W + x], ((unsigned long long)__float_as_uint(depth) << 32) | cold);
     };
 
+    // A band is drawn in rounds of phase A and phase B; one round unless a list fills.  A listed triangle is always
+    // drawn by phase B: a thread whose triangle a full list refuses ends its phase A there and takes it up again in
+    // the next round (tnext), after phase B has emptied the lists.  Which triangles the atomics refuse therefore
+    // changes no key: the two phases' arithmetic is contracted differently, and a refused triangle drawn by its own
+    // thread would carry phase A's depth bits into the image (DESIGN.md 3.7 "Synthetic meshes")
+    int tnext = tid;
+    for (;;) {
     // ---- phase A: one triangle per thread; large ones are listed for phase B
-    for (int t = tid; t < a.ntri; t += kRenderThreads) {
+    int t = tnext;
+    for (; t < a.ntri; t += kRenderThreads) {
       float sx[3], sy[3], iz[3];
       uint32_t col;
       int bx0, bx1, by0, by1;
@@ -497,21 +505,29 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
         if (boxpx >= kWideKeys) {
           const int k = atomicAdd(&nbig, 1);
           if (k < kBigCap) { big[k] = t; continue; }
+          break;
         } else if (boxpx > kBigPx) {
           const int k = atomicAdd(&nmid, 1);
           if (k < kCap - kBigCap) { big[kCap - 1 - k] = t; continue; }
+          break;
         }
       } else if (boxpx > kBigPx) {
         const int k = atomicAdd(&nbig, 1);
         if (k < kCap) { big[k] = t; continue; }
+        break;
       }
       for (int y = by0; y <= by1; y++)
         for (int x = bx0; x <= bx1; x++) raster(sx, sy, iz, col, x, y);
     }
+    tnext = t;
     __syncthreads();
+    // the lists' lengths of this round, read by every thread before thread 0 may reset them (uniform)
+    const int nlisted = nbig;
+    int nmlisted = 0;
+    if constexpr (kMsaa) nmlisted = nmid;
     // ---- phase B: each large triangle with all threads over its bbox
-    int nb = min(nbig, kCap);
-    if constexpr (kMsaa) nb = min(nbig, kBigCap);           // the wide list
+    int nb = min(nlisted, kCap);
+    if constexpr (kMsaa) nb = min(nlisted, kBigCap);        // the wide list
     for (int k = 0; k < nb; k++) {
       float sx[3], sy[3], iz[3];
       uint32_t col;
@@ -532,7 +548,7 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
     if constexpr (kMsaa) {
       // the other list: a triangle per wave, its lanes over (sample, box pixel).  These are a few wavefuls of keys each,
       // and setting one up in every thread of the block costs more than drawing it
-      const int nm = min(nmid, kCap - kBigCap);
+      const int nm = min(nmlisted, kCap - kBigCap);
       for (int k = tid / kWave; k < nm; k += kRenderThreads / kWave) {
         float sx[3], sy[3], iz[3];
         uint32_t col;
@@ -547,6 +563,16 @@ __global__ void __launch_bounds__(kRenderThreads) so100_render_kernel(Args a) {
       }
     }
     __syncthreads();
+    // another round when a list refused triangles (uniform: every thread read the same lengths)
+    bool more = nlisted > kCap;
+    if constexpr (kMsaa) more = nlisted > kBigCap || nmlisted > kCap - kBigCap;
+    if (!more) break;
+    if (tid == 0) nbig = 0;
+    if constexpr (kMsaa) {
+      if (tid == 0) nmid = 0;
+    }
+    __syncthreads();
+    }
     if constexpr (kMsaa) {
       // ---- the resolve: per pixel and channel (sum of the S samples' bytes + S / 2) / S, an empty sample 0.  The result
       // goes to plane 0 as a key with the colour in its place and the upper half 0 (never the empty key), which the

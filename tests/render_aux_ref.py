@@ -79,9 +79,12 @@ def _tracking_frame(pos, target, dt):
     return np.stack([x, np.cross(z, x), z], axis=1).astype(dt)
 
 
-def render(scene_tri, scene_body, scene_rgb, label, frames, cam, width, height, target=None, dtype=np.float64):
+def render(scene_tri, scene_body, scene_rgb, label, frames, cam, width, height, target=None, dtype=np.float64,
+           winner=False):
     """frames: [NBODY] of (R [3,3], p [3]); label: uint8 [T]; cam: render_ref.camera_dict's dict; target: the tracked
-    point of a tracking camera.  Returns (rgb uint8 [H,W,3], depth float32 [H,W], label uint8 [H,W])."""
+    point of a tracking camera.  Returns (rgb uint8 [H,W,3], depth float32 [H,W], label uint8 [H,W]) and with
+    winner=True a fourth, int32 [H,W]: the index of the triangle whose key the pixel holds (the first of equal keys),
+    -1 on the background."""
     dt = np.dtype(dtype).type
     cam = dict(cam, pos=np.asarray(cam["pos"], dt), mat=np.asarray(cam["mat"], dt), fovy=dt(cam["fovy"]),
                znear=dt(cam["znear"]), head_ambient=dt(cam["head_ambient"]), head_diffuse=dt(cam["head_diffuse"]),
@@ -104,6 +107,7 @@ def render(scene_tri, scene_body, scene_rgb, label, frames, cam, width, height, 
     col = _shade(cam, w, render_ref.pack_rgb(scene_rgb), dt)
     low = (col.astype(np.uint64) << np.uint64(8)) | np.asarray(label, np.uint64)
     key = np.full((height, width), EMPTY, np.uint64)
+    win = np.full((height, width), -1, np.int32)
     half = dt(0.5)
     for t in np.nonzero(ok)[0]:
         x, y, z = sx[t], sy[t], iz[t]
@@ -125,13 +129,14 @@ def render(scene_tri, scene_body, scene_rgb, label, frames, cam, width, height, 
         dep = (dt(1.0) / np.where(inside, izp, dt(1.0))).astype(np.float32)
         k = (dep.view(np.uint32).astype(np.uint64) << np.uint64(32)) | low[t]
         sub = key[by0:by1 + 1, bx0:bx1 + 1]
+        np.copyto(win[by0:by1 + 1, bx0:bx1 + 1], np.int32(t), where=inside & (k < sub))
         np.copyto(sub, np.minimum(sub, k), where=inside)
     empty = key == EMPTY
     rgb = np.where(empty, np.uint64(0), (key >> np.uint64(8)) & np.uint64(0xFFFFFF)).astype(np.uint32)
     img = np.stack([(rgb >> (8 * k)) & 0xFF for k in range(3)], axis=-1).astype(np.uint8)
     dep = np.where(empty, np.uint64(0), key >> np.uint64(32)).astype(np.uint32).view(np.float32)
     lab = (key & np.uint64(0xFF)).astype(np.uint8)             # the empty key's low byte is 255
-    return img, dep, lab
+    return (img, dep, lab, win) if winner else (img, dep, lab)
 
 
 _CACHE = {}

@@ -35,12 +35,15 @@ def resolve(samples):
     return ((samples.astype(np.uint32).sum(axis=0) + S // 2) // S).astype(np.uint8)
 
 
-def raster(sx, sy, iz, ok, col, width, height, offsets, dt):
+def raster(sx, sy, iz, ok, col, width, height, offsets, dt, winner=False):
     """The sample keys of set-up triangles: sx, sy, iz [T, 3] screen vertices and inverse depths, ok [T] (every vertex
-    beyond znear), col [T] packed RGB.  Returns uint8 [S, H, W, 3], the colour every sample holds (empty: 0)."""
+    beyond znear), col [T] packed RGB.  Returns uint8 [S, H, W, 3], the colour every sample holds (empty: 0), and with
+    winner=True also int32 [S, H, W]: the index of the triangle whose key the sample holds (the first of equal keys),
+    -1 for an empty sample."""
     off = np.asarray(offsets, np.float64).astype(dt)
     S = len(off)
     key = np.full((S, height, width), EMPTY, np.uint64)
+    win = np.full((S, height, width), -1, np.int32)
     half = dt(0.5)
     oxlo, oxhi, oylo, oyhi = off[:, 0].min(), off[:, 0].max(), off[:, 1].min(), off[:, 1].max()
     for t in np.nonzero(ok)[0]:
@@ -67,14 +70,17 @@ def raster(sx, sy, iz, ok, col, width, height, offsets, dt):
             dep = (dt(1.0) / np.where(inside, izp, dt(1.0))).astype(np.float32)
             k = (dep.view(np.uint32).astype(np.uint64) << np.uint64(32)) | np.uint64(col[t])
             sub = key[s, by0:by1 + 1, bx0:bx1 + 1]
+            np.copyto(win[s, by0:by1 + 1, bx0:bx1 + 1], np.int32(t), where=inside & (k < sub))
             np.copyto(sub, np.minimum(sub, k), where=inside)
     rgb = np.where(key == EMPTY, np.uint64(0), key & np.uint64(0xFFFFFF)).astype(np.uint32)
-    return np.stack([(rgb >> (8 * k)) & 0xFF for k in range(3)], axis=-1).astype(np.uint8)
+    smp = np.stack([(rgb >> (8 * k)) & 0xFF for k in range(3)], axis=-1).astype(np.uint8)
+    return (smp, win) if winner else smp
 
 
-def render(scene_tri, scene_body, scene_rgb, frames, cam, width, height, offsets, target=None, dtype=np.float64):
+def render(scene_tri, scene_body, scene_rgb, frames, cam, width, height, offsets, target=None, dtype=np.float64,
+           winner=False):
     """render_aux_ref.render's arguments without the labels, plus offsets [S][2].  Returns (rgb uint8 [H,W,3] resolved,
-    samples uint8 [S,H,W,3])."""
+    samples uint8 [S,H,W,3]) and with winner=True a third, int32 [S,H,W]: each sample's winning triangle (-1: empty)."""
     dt = np.dtype(dtype).type
     cam = dict(cam, pos=np.asarray(cam["pos"], dt), mat=np.asarray(cam["mat"], dt), fovy=dt(cam["fovy"]),
                znear=dt(cam["znear"]), head_ambient=dt(cam["head_ambient"]), head_diffuse=dt(cam["head_diffuse"]),
@@ -94,6 +100,9 @@ def render(scene_tri, scene_body, scene_rgb, frames, cam, width, height, offsets
     sx = (c[..., 0] * iz / (th * aspect) * dt(0.5) + dt(0.5)) * dt(width)
     sy = (dt(0.5) - c[..., 1] * iz / th * dt(0.5)) * dt(height)
     col = A._shade(cam, w, render_ref.pack_rgb(scene_rgb), dt)
+    if winner:
+        smp, win = raster(sx, sy, iz, ok, col, width, height, offsets, dt, winner=True)
+        return resolve(smp), smp, win
     smp = raster(sx, sy, iz, ok, col, width, height, offsets, dt)
     return resolve(smp), smp
 

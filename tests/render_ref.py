@@ -45,9 +45,10 @@ def tracking_frame(pos, target):
     return np.stack([x, np.cross(z, x), z], axis=1)
 
 
-def render(scene_tri, scene_body, scene_rgb, frames, cam, width, height, target=None):
+def render(scene_tri, scene_body, scene_rgb, frames, cam, width, height, target=None, winner=False):
     """frames: [NBODY] of (R [3,3], p [3]) world frames; target: the tracked point (ee_site) of a
-    tracking camera; returns uint8 [H, W, 3]."""
+    tracking camera; returns uint8 [H, W, 3], with winner=True also int32 [H, W]: the index of the triangle
+    whose key the pixel holds (the first of equal keys), -1 on the background."""
     if cam.get("track"):
         cam = dict(cam, mat=tracking_frame(cam["pos"], target))
     R = np.stack([f[0] for f in frames])[scene_body]                   # [T,3,3]
@@ -64,6 +65,7 @@ def render(scene_tri, scene_body, scene_rgb, frames, cam, width, height, target=
     sy = (0.5 - c[..., 1] * iz / th * 0.5) * height
     col = shade(cam, w, pack_rgb(scene_rgb))
     key = np.full((height, width), np.iinfo(np.uint64).max, np.uint64)
+    win = np.full((height, width), -1, np.int32)
     for t in np.nonzero(ok)[0]:
         x, y, z = sx[t], sy[t], iz[t]
         area = (x[1] - x[0]) * (y[2] - y[0]) - (x[2] - x[0]) * (y[1] - y[0])
@@ -84,9 +86,11 @@ def render(scene_tri, scene_body, scene_rgb, frames, cam, width, height, target=
         dep = (1.0 / np.where(inside, izp, 1.0)).astype(np.float32)
         k = (dep.view(np.uint32).astype(np.uint64) << np.uint64(32)) | np.uint64(col[t])
         sub = key[by0:by1 + 1, bx0:bx1 + 1]
+        np.copyto(win[by0:by1 + 1, bx0:bx1 + 1], np.int32(t), where=inside & (k < sub))
         np.copyto(sub, np.minimum(sub, k), where=inside)
     rgb = np.where(key == np.iinfo(np.uint64).max, np.uint64(0), key & np.uint64(0xFFFFFF)).astype(np.uint32)
-    return np.stack([(rgb >> (8 * k)) & 0xFF for k in range(3)], axis=-1).astype(np.uint8)
+    img = np.stack([(rgb >> (8 * k)) & 0xFF for k in range(3)], axis=-1).astype(np.uint8)
+    return (img, win) if winner else img
 
 
 def camera_dict(cam_struct):
