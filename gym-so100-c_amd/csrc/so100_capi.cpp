@@ -77,6 +77,10 @@ hipError_t launch_her_push(const so100_her&, const so100_her_step&, hipStream_t)
 hipError_t launch_her_discard(const so100_her&, const uint8_t*, const float*, const float*, hipStream_t);
 hipError_t launch_her_scan(const so100_her&, hipStream_t);
 hipError_t launch_her_sample(const DevModel*, const so100_her&, const so100_her_out&, int, int, uint64_t, hipStream_t);
+hipError_t launch_replay_push(const so100_replay&, const so100_replay_step&, hipStream_t);
+hipError_t launch_replay_stage(const so100_replay&, const uint8_t*, const float*, const uint8_t*, hipStream_t);
+hipError_t launch_replay_scan(const so100_replay&, hipStream_t);
+hipError_t launch_replay_sample(const so100_replay&, const so100_replay_out&, int, uint64_t, hipStream_t);
 }  // namespace so100
 
 using so100::DevModel;
@@ -1787,6 +1791,103 @@ static int so100_her_sample_impl(so100_env* env, const so100_her* h, int batch, 
   return e == hipSuccess ? 0 : fail_hip(fn, e);
 }
 
+// the checks every so100_replay_* call shares (include/so100.h): the record's numbers first, then (replay_check_ptrs,
+// after the call's own records) the env and the arrays
+static int replay_check(const char* fn, const so100_replay* h) {
+  if (!h) return her_fail(fn, "NULL replay");
+  if (h->size != sizeof(so100_replay)) return size_mismatch(fn, "so100_replay", h->size, sizeof(so100_replay));
+  if (h->T < 2) return her_fail(fn, "T < 2");
+  if (h->n < 0) return her_fail(fn, "n < 0");
+  if ((long long)h->T * h->n >= (1ll << 31)) return her_fail(fn, "T * n >= 2^31");
+  if (h->action_dim < 1 || h->action_dim > SO100_REPLAY_MAX_ACTION) return her_fail(fn, "action_dim outside 1..16");
+  bool shape_ok;
+  if (h->P == 0) {
+    shape_ok = h->planes == 0 && h->H == 0 && h->W == 0 && h->chan == 0;
+  } else {
+    shape_ok = h->P > 0 && h->planes >= 1 && h->H >= 1 && h->W >= 1 && h->chan >= 1;
+    // (each factor <= P < 2^31: the product is formed stepwise in 64 bits and cut off as soon as it passes P)
+    long long prod = 1;
+    const int32_t f[4] = {h->planes, h->H, h->W, h->chan};
+    for (int k = 0; shape_ok && k < 4; k++) {
+      prod *= f[k];
+      if (prod > h->P) shape_ok = false;
+    }
+    if (shape_ok && prod != h->P) shape_ok = false;
+  }
+  if (!shape_ok) return her_fail(fn, "planes, H, W, chan and P do not agree");
+  if (h->pad < 0 || h->pad > SO100_REPLAY_MAX_PAD) return her_fail(fn, "pad outside 0..64");
+  if (h->pad != 0 && h->P == 0) return her_fail(fn, "pad without images");
+  return 0;
+}
+static int replay_check_ptrs(const char* fn, const so100_env* env, const so100_replay* h) {
+  if (!env) return her_fail(fn, "NULL env");
+  if (!h->obs || !h->next_obs || !h->action || !h->reward || !h->terminated || !h->meta || !h->prefix)
+    return her_fail(fn, "NULL array in so100_replay");
+  if (h->P == 0 && (h->obs_img || h->next_img)) return her_fail(fn, "image arrays in so100_replay with P == 0");
+  if (h->P > 0 && (!h->obs_img || !h->next_img)) return her_fail(fn, "NULL image array in so100_replay with P > 0");
+  return 0;
+}
+
+static int so100_replay_push_impl(so100_env* env, const so100_replay* h, const so100_replay_step* st, void* stream) {
+  const char* fn = "so100_replay_push";
+  if (int rc = replay_check(fn, h)) return rc;
+  if (!st) return her_fail(fn, "NULL step");
+  if (st->size != sizeof(so100_replay_step))
+    return size_mismatch(fn, "so100_replay_step", st->size, sizeof(so100_replay_step));
+  if (int rc = replay_check_ptrs(fn, env, h)) return rc;
+  if (!st->obs || !st->final_obs || !st->action || !st->reward || !st->terminated || !st->truncated)
+    return her_fail(fn, "NULL pointer in so100_replay_step");
+  if (h->P == 0 && (st->pixels || st->final_pixels)) return her_fail(fn, "image pointers in so100_replay_step with P == 0");
+  if (h->P > 0 && (!st->pixels || !st->final_pixels))
+    return her_fail(fn, "NULL image pointer in so100_replay_step with P > 0");
+  if (h->n == 0) return 0;
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_replay_push(*h, *st, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip(fn, e);
+}
+
+static int so100_replay_stage_impl(so100_env* env, const so100_replay* h, const uint8_t* mask, const float* obs,
+                                   const uint8_t* pixels, void* stream) {
+  const char* fn = "so100_replay_stage";
+  if (int rc = replay_check(fn, h)) return rc;
+  if (int rc = replay_check_ptrs(fn, env, h)) return rc;
+  if (!obs) return her_fail(fn, "NULL obs");
+  if (h->P == 0 && pixels) return her_fail(fn, "pixels with P == 0");
+  if (h->P > 0 && !pixels) return her_fail(fn, "NULL pixels with P > 0");
+  if (h->n == 0) return 0;
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_replay_stage(*h, mask, obs, pixels, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip(fn, e);
+}
+
+static int so100_replay_scan_impl(so100_env* env, const so100_replay* h, void* stream) {
+  const char* fn = "so100_replay_scan";
+  if (int rc = replay_check(fn, h)) return rc;
+  if (int rc = replay_check_ptrs(fn, env, h)) return rc;
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_replay_scan(*h, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip(fn, e);
+}
+
+static int so100_replay_sample_impl(so100_env* env, const so100_replay* h, int batch, uint64_t call,
+                                    const so100_replay_out* o, void* stream) {
+  const char* fn = "so100_replay_sample";
+  if (int rc = replay_check(fn, h)) return rc;
+  if (batch < 0) return her_fail(fn, "batch < 0");
+  if (!o) return her_fail(fn, "NULL out");
+  if (o->size != sizeof(so100_replay_out)) return size_mismatch(fn, "so100_replay_out", o->size, sizeof(so100_replay_out));
+  if (int rc = replay_check_ptrs(fn, env, h)) return rc;
+  if (!o->obs || !o->next_obs || !o->actions || !o->rewards || !o->dones || !o->env || !o->slot || !o->shift)
+    return her_fail(fn, "NULL pointer in so100_replay_out");
+  if (h->P == 0 && (o->pixels || o->next_pixels)) return her_fail(fn, "image pointers in so100_replay_out with P == 0");
+  if (h->P > 0 && (!o->pixels || !o->next_pixels))
+    return her_fail(fn, "NULL image pointer in so100_replay_out with P > 0");
+  if (batch == 0) return 0;
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_replay_sample(*h, *o, batch, call, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip(fn, e);
+}
+
 static int so100_norm_return_impl(so100_env* env, const so100_norm_ret* a, int n, const float* reward,
                                   const uint8_t* terminated, const uint8_t* truncated, double* ret, double* stats,
                                   void* work, float* reward_norm, void* stream) {
@@ -1911,6 +2012,54 @@ int so100_her_sample(so100_env* env, const so100_her* her, int batch, uint64_t c
     return so100_her_sample_impl(env, her, batch, call, out, stream);
   } catch (...) {
     return caught("so100_her_sample");
+  }
+}
+
+int so100_replay_bytes(void) { return (int)sizeof(so100_replay); }
+int so100_replay_step_bytes(void) { return (int)sizeof(so100_replay_step); }
+int so100_replay_out_bytes(void) { return (int)sizeof(so100_replay_out); }
+
+int64_t so100_replay_storage_bytes(int n, int T, int action_dim, int P) {
+  if (n < 0 || T < 2 || (long long)T * n >= (1ll << 31) || action_dim < 1 || action_dim > SO100_REPLAY_MAX_ACTION ||
+      P < 0) {
+    fail("so100_replay_storage_bytes: n < 0, T < 2, T * n >= 2^31, action_dim outside 1..16 or P < 0");
+    return -1;
+  }
+  const int64_t slots = (int64_t)T * n;
+  return slots * (4 * (SO100_NOBS + SO100_NOBS + action_dim + 1) + 1 + 2 * (int64_t)P) + 4 * (2 * (int64_t)n + n + 1);
+}
+
+int so100_replay_push(so100_env* env, const so100_replay* replay, const so100_replay_step* step, void* stream) {
+  try {
+    return so100_replay_push_impl(env, replay, step, stream);
+  } catch (...) {
+    return caught("so100_replay_push");
+  }
+}
+
+int so100_replay_stage(so100_env* env, const so100_replay* replay, const uint8_t* mask, const float* obs,
+                       const uint8_t* pixels, void* stream) {
+  try {
+    return so100_replay_stage_impl(env, replay, mask, obs, pixels, stream);
+  } catch (...) {
+    return caught("so100_replay_stage");
+  }
+}
+
+int so100_replay_scan(so100_env* env, const so100_replay* replay, void* stream) {
+  try {
+    return so100_replay_scan_impl(env, replay, stream);
+  } catch (...) {
+    return caught("so100_replay_scan");
+  }
+}
+
+int so100_replay_sample(so100_env* env, const so100_replay* replay, int batch, uint64_t call, const so100_replay_out* out,
+                        void* stream) {
+  try {
+    return so100_replay_sample_impl(env, replay, batch, call, out, stream);
+  } catch (...) {
+    return caught("so100_replay_sample");
   }
 }
 

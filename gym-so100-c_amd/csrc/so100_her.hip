@@ -29,6 +29,7 @@
 #include "so100.h"
 #include "so100_device.h"
 #include "so100_goal.h"
+#include "so100_ring.h"
 
 namespace so100 {
 
@@ -47,32 +48,6 @@ int her_scan_group() { return kScanThreads; }
 int her_scan_tile() { return kScanTile; }
 
 namespace {
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
-// the 64-bit draw of (seed, sample call, batch element, field): so100_views_sample's key with the call in the
-// episode's place
-__device__ __forceinline__ uint64_t her_draw(uint64_t seed, uint64_t call, uint64_t i, uint32_t field) {
-  const uint64_t k = splitmix64(seed ^ (i * 0x100000001B3ull) ^ ((uint64_t)field * 0xD1B54A32D192ED03ull));
-  return splitmix64(k + call);
-}
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// (a + b) mod T and (a - b) mod T for a in [0, T), b in [0, T]
-__device__ __forceinline__ int add_mod(int a, int b, int T) {
-  const int s = a - (T - b);                             // (not a + b - T: a + b can pass 2^31)
-  return s >= 0 ? s : s + T;
-}
-__device__ __forceinline__ int sub_mod(int a, int b, int T) {
-  const int s = a - b;
-  return s >= 0 ? s : s + T;
-}
 
 struct HerMeta {
   int lo, count, open;
@@ -300,6 +275,11 @@ hipError_t launch_her_discard(const so100_her& h, const uint8_t* mask, const flo
 
 hipError_t launch_her_scan(const so100_her& h, hipStream_t s) {
   hipLaunchKernelGGL(so100_her_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, h.n, h.T, h.meta + h.n, h.prefix);
+  return hipGetLastError();
+}
+
+hipError_t launch_count_scan(int n, int cap, const int32_t* count, int32_t* prefix, hipStream_t s) {
+  hipLaunchKernelGGL(so100_her_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, n, cap, count, prefix);
   return hipGetLastError();
 }
 

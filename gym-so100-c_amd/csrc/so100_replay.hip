@@ -1,0 +1,411 @@
+// so100_replay.hip - a uniform replay buffer for the arm tasks on the device, for state and pixel observations (C-ABI
+// so100_replay_push, so100_replay_stage, so100_replay_scan, so100_replay_sample; include/so100.h states the rules,
+// DESIGN.md §3.12 the reasons).  New launches beside the untouched step kernel: a push copies what the step and the
+// rasteriser left (15 floats, the command, the scalars and, with P > 0, the P bytes of the env's images) into the env's
+// ring, a sample draws uniformly among the valid transitions and, with pad > 0, shifts the two images of each row by
+// independent random offsets (DrQ's replicate-pad and crop) while it gathers them.  No atomics, no wait for another
+// workgroup, plain vector stores; every result is a function of the inputs alone.  No LDS.
+//
+// Addressing.  Rows of P bytes start at (slot n + e) P and i P: byte offsets are 64-bit, and neither P nor a row start is
+// a multiple of 4 in general.  Every access wider than a byte is naturally aligned: stores go to the 4-aligned words of
+// the destination row (its 0..3 head bytes and 0..3 tail bytes singly), and the 4 source bytes of such a word come from
+// the one or two aligned words that hold them, joined by v_alignbyte_b32.  An aligned word that holds one byte of an
+// array lies in that byte's page, so the join never touches an unmapped page.  Where the rows and P are all multiples of
+// 16 (every real image size) the copy moves 16 bytes per lane instead.
+//
+// Push and stage.  One workgroup per env (256 threads with images, 64 without): thread c < 15 copies column c of the
+// observation, threads 16.. the command, thread 32 the scalars, and all of them the image rows.  An env that did not
+// finish reads its `pixels` row once and stores it twice (next_img at the cursor, obs_img at the new cursor) when the two
+// destinations agree mod 4 (always when P is a multiple of 4); a finished env copies final_pixels and pixels once each.
+// The metadata: every thread reads cursor and count first, a workgroup barrier follows the copies, thread 0 then writes
+// them; no other workgroup of the launch touches this env.
+//
+// Sample.  One launch of two kinds of workgroups.  The first ceil(B / 16) take the float rows, 16 lanes per batch element
+// as in so100_her.hip.  The others take the images in pieces of one output image, `span` chunks of kChunk bytes each,
+// spread over a grid of at most kMaxPieceGroups workgroups.  Every workgroup repeats the draw and the search of its row:
+// a chain of dependent loads that hit L2, which is what a piece costs before its first byte moves.  So each wave searches
+// the prefix sums 64 ways at a time (3 rounds for 8,192 envs, not 13), and the launcher grows `span` with the batch (one
+// chunk per piece up to kSpanPieces pieces, then more).  A thread builds 4-aligned output words, 4 per chunk: with
+// pad == 0 by the aligned join above, with pad > 0 from 4 byte loads at the clamped source coordinates, found by two
+// divisions per word and increments between its bytes.  The stores are contiguous 256-byte runs per wave; the loads are
+// rows of the ring, each source byte fetched from HBM once and again only from L1 / L2.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "so100.h"
+#include "so100_ring.h"
+
+namespace so100 {
+
+constexpr int kRepThreads = 256;
+constexpr int kRepStateThreads = 64;                     // push / stage without images
+constexpr int kRepLanes = 16;                            // lanes per batch element (the sample's float rows)
+constexpr int kRepRows = kRepThreads / kRepLanes;
+constexpr int kRepObs = SO100_NOBS;
+constexpr int kChunk = 4096;                             // output bytes of one image piece
+constexpr int kChunkWords = kChunk / 4;
+constexpr unsigned kMaxPieceGroups = 1u << 20;
+constexpr long long kSpanPieces = 8192;                  // pieces of one chunk beyond which a piece takes more chunks
+static_assert(kRepObs < kRepLanes, "a row's columns and one scalar lane fit the lanes of a batch element");
+static_assert(SO100_REPLAY_MAX_ACTION <= kRepLanes, "one lane per command component");
+static_assert(16 + SO100_REPLAY_MAX_ACTION <= 32 && 32 < kRepStateThreads, "the push's thread roles fit one wave");
+static_assert(kChunkWords % kRepThreads == 0, "a piece is a whole number of words per thread");
+
+namespace {
+
+// the 4 bytes at s (any alignment) from the aligned words that hold them
+__device__ __forceinline__ uint32_t load4(const uint8_t* s) {
+  const uintptr_t a = (uintptr_t)s;
+  const uint32_t* w = (const uint32_t*)(a & ~(uintptr_t)3);
+  const uint32_t sh = (uint32_t)(a & 3);
+  const uint32_t w0 = w[0];
+  const uint32_t w1 = sh != 0 ? w[1] : 0u;
+  return __builtin_amdgcn_alignbyte(w1, w0, sh);
+}
+
+// dst[0..P) (and dst2[0..P) where TWO; dst2 = dst mod 4) <- src[0..P), by the nt threads of a workgroup
+template <bool TWO>
+__device__ __forceinline__ void copy_row(uint8_t* dst, uint8_t* dst2, const uint8_t* src, int P, int tid, int nt) {
+  const uintptr_t all = (uintptr_t)dst | (uintptr_t)src | (TWO ? (uintptr_t)dst2 : 0) | (uintptr_t)(uint32_t)P;
+  if ((all & 15) == 0) {
+    const uint4* s16 = (const uint4*)src;
+    uint4* d16 = (uint4*)dst;
+    uint4* e16 = (uint4*)dst2;
+    const int nq = P >> 4;
+    for (int q = tid; q < nq; q += nt) {
+      const uint4 v = s16[q];
+      d16[q] = v;
+      if (TWO) e16[q] = v;
+    }
+    return;
+  }
+  const int align = (int)((0 - (uintptr_t)dst) & 3);
+  const int head = align < P ? align : P;
+  const int nw = (P - head) >> 2;
+  const int tail0 = head + 4 * nw;
+  if (tid < head) {
+    const uint8_t v = src[tid];
+    dst[tid] = v;
+    if (TWO) dst2[tid] = v;
+  }
+  if (tail0 + tid < P) {                                 // (at most 3 bytes)
+    const uint8_t v = src[tail0 + tid];
+    dst[tail0 + tid] = v;
+    if (TWO) dst2[tail0 + tid] = v;
+  }
+  uint32_t* dw = (uint32_t*)(dst + head);
+  uint32_t* ew = (uint32_t*)(dst2 + head);
+  for (int w = tid; w < nw; w += nt) {
+    const uint32_t v = load4(src + head + 4 * (size_t)w);
+    dw[w] = v;
+    if (TWO) ew[w] = v;
+  }
+}
+
+struct RepPick {
+  int e, slot;
+  bool any;
+};
+
+// the first env e of [0, n) with prefix[e] > r (n - 1 when there is none), by bisection: any set of lanes
+__device__ __forceinline__ int find_env_bisect(const int32_t* prefix, int n, long long r) {
+  int lo = 0, hi = n - 1;
+  for (int it = 0; it < 32 && lo < hi; it++) {
+    const int mid = (int)(((long long)lo + hi) >> 1);
+    if ((long long)prefix[mid] > r) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+// the same env found by a whole wave (all 64 lanes active, r equal in all): each round the lanes probe 64 evenly spaced
+// candidates and a ballot narrows the range 64-fold, so 8,192 envs take 3 dependent loads where bisection takes 13
+__device__ __forceinline__ int find_env_wave(const int32_t* prefix, int n, long long r) {
+  const int lane = (int)threadIdx.x & 63;
+  int lo = 0, cnt = n;                                   // the candidates are [lo, lo + cnt)
+  for (int it = 0; it < 6 && cnt > 1; it++) {
+    const int step = (cnt + 63) >> 6;
+    const int last = lo + cnt - 1;
+    const long long want = (long long)lo + (long long)(lane + 1) * step - 1;
+    const int probe = want < last ? (int)want : last;    // nondecreasing in the lane, within [lo, last]
+    const bool below = (long long)prefix[probe] <= r;
+    const int f = __popcll(__ballot(below));             // the lanes whose probe is still <= r: the first f
+    if (f == 64) return last;                            // (no env of the range exceeds r)
+    const long long nlo = (long long)lo + (long long)f * step;       // one past lane f - 1's probe
+    if (nlo > last) return last;                         // (only a prefix array that does not ascend gets here)
+    const long long nhi = (long long)lo + (long long)(f + 1) * step - 1;
+    const int hi = nhi < last ? (int)nhi : last;
+    lo = f == 0 ? lo : (int)nlo;
+    cnt = hi - lo + 1;
+  }
+  return lo;
+}
+
+// the transition of batch element i: r uniform in [0, total), its env the first e with prefix[e] > r.  WAVE: called by
+// whole waves with one i per wave
+template <bool WAVE>
+__device__ __forceinline__ RepPick replay_pick(const so100_replay& h, uint64_t call, size_t i) {
+  RepPick p = {0, -1, false};
+  const int n = h.n, T = h.T;
+  const long long cap = (long long)(T - 1) * n;
+  long long total = h.prefix[n];
+  total = total < 0 ? 0 : (total > cap ? cap : total);
+  if (total == 0) return p;
+  const long long r = (long long)__umul64hi(her_draw(h.seed, call, i, 0u), (uint64_t)total);
+  const int e = WAVE ? find_env_wave(h.prefix, n, r) : find_env_bisect(h.prefix, n, r);
+  const long long base = e > 0 ? (long long)h.prefix[e - 1] : 0;
+  const long long kq = r - base;
+  const int k = (int)(kq < 0 ? 0 : (kq > T - 2 ? T - 2 : kq));
+  const int cur = clampi(h.meta[e], 0, T - 1);
+  const int cnt = clampi(h.meta[(size_t)n + e], 0, T - 1);
+  p.e = e;
+  p.slot = add_mod(sub_mod(cur, cnt, T), k, T);
+  p.any = true;
+  return p;
+}
+
+// (dx, dy) of the 64-bit draw h for S = 2 pad + 1 offsets
+__device__ __forceinline__ void replay_shift(uint64_t h, int S, int& dx, int& dy) {
+  dx = (int)(((h & 0xFFFFFFFFull) * (uint64_t)S) >> 32);
+  dy = (int)(((h >> 32) * (uint64_t)S) >> 32);
+}
+
+// the coordinates of one output byte, stepped through the image in memory order
+struct RepCoord {
+  int q, y, x, c;                                        // q = p H: the first row of the byte's plane
+  __device__ __forceinline__ void set(int k, int H, int W, int chan) {
+    const int rowbytes = W * chan;
+    const int row = k / rowbytes, cb = k - row * rowbytes;
+    const int p = row / H;
+    q = p * H;
+    y = row - q;
+    x = cb / chan;
+    c = cb - x * chan;
+  }
+  __device__ __forceinline__ void next(int H, int W, int chan) {
+    if (++c == chan) {
+      c = 0;
+      if (++x == W) {
+        x = 0;
+        if (++y == H) {
+          y = 0;
+          q += H;
+        }
+      }
+    }
+  }
+  // the source byte's offset under the shift (ox, oy) = (dx - pad, dy - pad)
+  __device__ __forceinline__ int source(int ox, int oy, int H, int W, int chan) const {
+    const int sy = clampi(y + oy, 0, H - 1), sx = clampi(x + ox, 0, W - 1);
+    return ((q + sy) * W + sx) * chan + c;               // < P < 2^31
+  }
+};
+
+}  // namespace
+
+__global__ __launch_bounds__(kRepThreads) void so100_replay_push_kernel(so100_replay h, so100_replay_step s) {
+  const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
+  const int e = (int)blockIdx.x, n = h.n, T = h.T, A = h.action_dim, P = h.P;
+  const int c = clampi(h.meta[e], 0, T - 1);
+  const int k = clampi(h.meta[(size_t)n + e], 0, T - 1);
+  const bool done = s.terminated[e] != 0 || s.truncated[e] != 0;
+  const bool drop = s.diverged != nullptr && s.diverged[e] != 0;
+  const int c2 = drop ? c : (c + 1 == T ? 0 : c + 1);
+  const int k2 = drop ? k : (k + 1 < T - 1 ? k + 1 : T - 1);
+  const size_t row = (size_t)c * n + e, row2 = (size_t)c2 * n + e;     // < T n < 2^31
+  if (tid < kRepObs) {
+    const float now = s.obs[(size_t)e * kRepObs + tid];
+    const float next = done ? s.final_obs[(size_t)e * kRepObs + tid] : now;
+    h.next_obs[row * kRepObs + tid] = next;              // 1.
+    h.obs[row2 * kRepObs + tid] = now;                   // 4.
+  }
+  if (tid >= 16 && tid < 16 + A) h.action[row * A + (tid - 16)] = s.action[(size_t)e * A + (tid - 16)];
+  if (tid == 32) {
+    h.reward[row] = s.reward[e];
+    h.terminated[row] = s.terminated[e] != 0 ? 1 : 0;
+  }
+  if (P > 0) {
+    const uint8_t* now = s.pixels + (size_t)e * P;
+    uint8_t* nxt = h.next_img + row * P;
+    uint8_t* stage = h.obs_img + row2 * P;
+    if (!done && (((uintptr_t)nxt ^ (uintptr_t)stage) & 3) == 0) {
+      copy_row<true>(nxt, stage, now, P, tid, nt);
+    } else {
+      copy_row<false>(nxt, nullptr, done ? s.final_pixels + (size_t)e * P : now, P, tid, nt);
+      copy_row<false>(stage, nullptr, now, P, tid, nt);
+    }
+  }
+  __syncthreads();                                       // every read of meta[e] is above, in every thread
+  if (tid == 0) {
+    h.meta[e] = c2;
+    h.meta[(size_t)n + e] = k2;
+  }
+}
+
+__global__ __launch_bounds__(kRepThreads) void so100_replay_stage_kernel(so100_replay h, const uint8_t* __restrict__ mask,
+                                                                         const float* __restrict__ obs,
+                                                                         const uint8_t* __restrict__ pixels) {
+  const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
+  const int e = (int)blockIdx.x, n = h.n, T = h.T, P = h.P;
+  if (mask != nullptr && mask[e] == 0) return;
+  const int c = clampi(h.meta[e], 0, T - 1);
+  const size_t row = (size_t)c * n + e;
+  if (tid < kRepObs) h.obs[row * kRepObs + tid] = obs[(size_t)e * kRepObs + tid];
+  if (P > 0) copy_row<false>(h.obs_img + row * P, nullptr, pixels + (size_t)e * P, P, tid, nt);
+}
+
+__global__ __launch_bounds__(kRepThreads) void so100_replay_sample_kernel(so100_replay h, so100_replay_out o, int batch,
+                                                                          uint64_t call, unsigned row_groups, int chunks,
+                                                                          int span) {
+  const int n = h.n, A = h.action_dim, P = h.P, pad = h.pad;
+  if (blockIdx.x < row_groups) {
+    // ---- the float rows, 16 lanes per batch element
+    const int c = (int)threadIdx.x & (kRepLanes - 1);
+    const long long il = (long long)blockIdx.x * kRepRows + ((int)threadIdx.x >> 4);
+    if (il >= batch) return;
+    const size_t i = (size_t)il;
+    const bool scalar = c == kRepLanes - 1;
+    const RepPick p = replay_pick<false>(h, call, i);
+    if (!p.any) {                                        // an empty buffer: zeros, nothing of the ring is read
+      if (c < kRepObs) {
+        o.obs[i * kRepObs + c] = 0.f;
+        o.next_obs[i * kRepObs + c] = 0.f;
+      }
+      if (c < A) o.actions[i * A + c] = 0.f;
+      if (c < 4) o.shift[i * 4 + c] = 0;
+      if (scalar) {
+        o.rewards[i] = 0.f;
+        o.dones[i] = 0.f;
+        o.env[i] = 0;
+        o.slot[i] = -1;
+      }
+      return;
+    }
+    const size_t row = (size_t)p.slot * n + p.e;
+    if (c < kRepObs) {
+      o.obs[i * kRepObs + c] = h.obs[row * kRepObs + c];
+      o.next_obs[i * kRepObs + c] = h.next_obs[row * kRepObs + c];
+    }
+    if (c < A) o.actions[i * A + c] = h.action[row * A + c];
+    if (c < 4) {
+      int d[4] = {pad, pad, pad, pad};
+      if (pad > 0) {
+        replay_shift(her_draw(h.seed, call, i, 2u), 2 * pad + 1, d[0], d[1]);
+        replay_shift(her_draw(h.seed, call, i, 3u), 2 * pad + 1, d[2], d[3]);
+      }
+      o.shift[i * 4 + c] = c == 0 ? d[0] : (c == 1 ? d[1] : (c == 2 ? d[2] : d[3]));
+    }
+    if (!scalar) return;
+    o.rewards[i] = h.reward[row];
+    o.dones[i] = h.terminated[row] != 0 ? 1.f : 0.f;
+    o.env[i] = p.e;
+    o.slot[i] = p.slot;
+    return;
+  }
+  // ---- the images: a piece is `span` chunks of kChunk bytes of one output image
+  const int tid = (int)threadIdx.x;
+  const int H = h.H, W = h.W, chan = h.chan;
+  const int groups = (chunks + span - 1) / span;
+  const long long per_row = 2ll * groups, pieces = (long long)batch * per_row;
+  const long long stride = (long long)gridDim.x - row_groups;
+  for (long long piece = (long long)blockIdx.x - row_groups; piece < pieces; piece += stride) {
+    const size_t i = (size_t)(piece / per_row);
+    const int rem = (int)(piece - (long long)i * per_row);
+    const int which = rem >= groups ? 1 : 0, grp = rem - which * groups;
+    const int ch0 = grp * span, ch1 = ch0 + span < chunks ? ch0 + span : chunks;
+    uint8_t* dst = (which ? o.next_pixels : o.pixels) + i * (size_t)P;
+    const int align = (int)((0 - (uintptr_t)dst) & 3);
+    const int head = align < P ? align : P;
+    const int nw = (P - head) >> 2;
+    const int tail0 = head + 4 * nw;
+    const bool ends = grp == 0;                          // this piece also takes the row's head and tail bytes
+    uint32_t* dw = (uint32_t*)(dst + head);
+    const RepPick p = replay_pick<true>(h, call, i);
+    if (!p.any) {
+      if (ends && tid < head) dst[tid] = 0;
+      if (ends && tail0 + tid < P) dst[tail0 + tid] = 0;
+      for (int ch = ch0; ch < ch1; ch++) {
+#pragma unroll
+        for (int u = 0; u < kChunkWords / kRepThreads; u++) {
+          const int w = ch * kChunkWords + u * kRepThreads + tid;
+          if (w < nw) dw[w] = 0u;
+        }
+      }
+      continue;
+    }
+    const uint8_t* src = (which ? h.next_img : h.obs_img) + ((size_t)p.slot * n + p.e) * (size_t)P;
+    if (pad == 0) {
+      if (ends && tid < head) dst[tid] = src[tid];
+      if (ends && tail0 + tid < P) dst[tail0 + tid] = src[tail0 + tid];
+      for (int ch = ch0; ch < ch1; ch++) {
+#pragma unroll
+        for (int u = 0; u < kChunkWords / kRepThreads; u++) {
+          const int w = ch * kChunkWords + u * kRepThreads + tid;
+          if (w < nw) dw[w] = load4(src + head + 4 * (size_t)w);
+        }
+      }
+      continue;
+    }
+    int dx, dy;
+    replay_shift(her_draw(h.seed, call, i, which ? 3u : 2u), 2 * pad + 1, dx, dy);
+    const int ox = dx - pad, oy = dy - pad;
+    RepCoord at;
+    if (ends && tid < head) {
+      at.set(tid, H, W, chan);
+      dst[tid] = src[at.source(ox, oy, H, W, chan)];
+    }
+    if (ends && tail0 + tid < P) {
+      at.set(tail0 + tid, H, W, chan);
+      dst[tail0 + tid] = src[at.source(ox, oy, H, W, chan)];
+    }
+    for (int ch = ch0; ch < ch1; ch++) {
+#pragma unroll
+      for (int u = 0; u < kChunkWords / kRepThreads; u++) {
+        const int w = ch * kChunkWords + u * kRepThreads + tid;
+        if (w < nw) {
+          at.set(head + 4 * w, H, W, chan);
+          uint32_t v = 0;
+#pragma unroll
+          for (int j = 0; j < 4; j++) {
+            v |= (uint32_t)src[at.source(ox, oy, H, W, chan)] << (8 * j);
+            at.next(H, W, chan);
+          }
+          dw[w] = v;
+        }
+      }
+    }
+  }
+}
+
+hipError_t launch_replay_push(const so100_replay& h, const so100_replay_step& st, hipStream_t s) {
+  hipLaunchKernelGGL(so100_replay_push_kernel, dim3((unsigned)h.n), dim3(h.P > 0 ? kRepThreads : kRepStateThreads), 0, s,
+                     h, st);
+  return hipGetLastError();
+}
+
+hipError_t launch_replay_stage(const so100_replay& h, const uint8_t* mask, const float* obs, const uint8_t* pixels,
+                               hipStream_t s) {
+  hipLaunchKernelGGL(so100_replay_stage_kernel, dim3((unsigned)h.n), dim3(h.P > 0 ? kRepThreads : kRepStateThreads), 0,
+                     s, h, mask, obs, pixels);
+  return hipGetLastError();
+}
+
+hipError_t launch_replay_scan(const so100_replay& h, hipStream_t s) {
+  return launch_count_scan(h.n, h.T - 1, h.meta + h.n, h.prefix, s);
+}
+
+hipError_t launch_replay_sample(const so100_replay& h, const so100_replay_out& o, int batch, uint64_t call,
+                                hipStream_t s) {
+  const unsigned row_groups = (unsigned)(((long long)batch + kRepRows - 1) / kRepRows);
+  const int chunks = (h.P + kChunk - 1) / kChunk;        // 0 without images
+  // a workgroup finds its row's transition once (the draw, a search of the prefix sums, the metadata: dependent loads),
+  // so a large batch gives it `span` chunks of the image for that price, a small one keeps the pieces small and many
+  const long long small = 2ll * chunks * batch;
+  long long span = (small + kSpanPieces - 1) / kSpanPieces;
+  span = span < 1 ? 1 : (span > chunks ? chunks : span);
+  const long long pieces = chunks > 0 ? 2ll * ((chunks + span - 1) / span) * batch : 0;
+  const unsigned piece_groups = (unsigned)(pieces < (long long)kMaxPieceGroups ? pieces : (long long)kMaxPieceGroups);
+  hipLaunchKernelGGL(so100_replay_sample_kernel, dim3(row_groups + piece_groups), dim3(kRepThreads), 0, s, h, o, batch,
+                     call, row_groups, chunks, (int)span);
+  return hipGetLastError();
+}
+
+}  // namespace so100

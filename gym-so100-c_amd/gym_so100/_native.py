@@ -256,6 +256,62 @@ class SO100HerOut(ctypes.Structure):
             setattr(self, name, p)
 
 
+SO100_REPLAY_MAX_ACTION = 16      # include/so100.h
+SO100_REPLAY_MAX_PAD = 64
+REPLAY_ARRAYS = ("obs", "next_obs", "action", "reward", "terminated", "obs_img", "next_img", "meta", "prefix")
+REPLAY_STEP_INPUTS = ("obs", "final_obs", "action", "reward", "terminated", "truncated", "diverged", "pixels",
+                      "final_pixels")
+REPLAY_OUTPUTS = ("obs", "next_obs", "actions", "rewards", "dones", "pixels", "next_pixels", "env", "slot", "shift")
+
+
+class SO100Replay(ctypes.Structure):
+    """Mirror of ``so100_replay`` (include/so100.h): the shape, the image layout, the sampling options and the device
+    arrays of one uniform replay buffer.  ``size`` is set to the mirror's size, which the callee checks against its
+    own."""
+    _fields_ = [("size", ctypes.c_uint32), ("n", ctypes.c_int32), ("T", ctypes.c_int32), ("action_dim", ctypes.c_int32),
+                ("planes", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("chan", ctypes.c_int32),
+                ("P", ctypes.c_int32), ("pad", ctypes.c_int32), ("seed", ctypes.c_uint64)] + \
+               [(name, _P) for name in REPLAY_ARRAYS]
+
+    def __init__(self, n=0, T=2, action_dim=6, planes=0, H=0, W=0, chan=0, P=0, pad=0, seed=0, **arrays):
+        super().__init__()
+        self.size = ctypes.sizeof(SO100Replay)
+        self.n, self.T, self.action_dim = int(n), int(T), int(action_dim)
+        self.planes, self.H, self.W, self.chan, self.P = int(planes), int(H), int(W), int(chan), int(P)
+        self.pad = int(pad)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        for name, p in arrays.items():
+            if name not in REPLAY_ARRAYS:
+                raise TypeError(f"so100_replay has no array {name!r}")
+            setattr(self, name, p)
+
+
+class SO100ReplayStep(ctypes.Structure):
+    """Mirror of ``so100_replay_step`` (include/so100.h): the device rows one ``so100_replay_push`` reads."""
+    _fields_ = [("size", ctypes.c_uint32), ("reserved0", ctypes.c_uint32)] + [(name, _P) for name in REPLAY_STEP_INPUTS]
+
+    def __init__(self, **inputs):
+        super().__init__()
+        self.size = ctypes.sizeof(SO100ReplayStep)
+        for name, p in inputs.items():
+            if name not in REPLAY_STEP_INPUTS:
+                raise TypeError(f"so100_replay_step has no input {name!r}")
+            setattr(self, name, p)
+
+
+class SO100ReplayOut(ctypes.Structure):
+    """Mirror of ``so100_replay_out`` (include/so100.h): the device arrays one ``so100_replay_sample`` fills."""
+    _fields_ = [("size", ctypes.c_uint32), ("reserved0", ctypes.c_uint32)] + [(name, _P) for name in REPLAY_OUTPUTS]
+
+    def __init__(self, **outputs):
+        super().__init__()
+        self.size = ctypes.sizeof(SO100ReplayOut)
+        for name, p in outputs.items():
+            if name not in REPLAY_OUTPUTS:
+                raise TypeError(f"so100_replay_out has no output {name!r}")
+            setattr(self, name, p)
+
+
 SO100_NMATERIAL = 5
 
 
@@ -384,6 +440,16 @@ def load():
     lib.so100_her_scan.argtypes = [_P, ctypes.POINTER(SO100Her), _P]
     lib.so100_her_sample.argtypes = [_P, ctypes.POINTER(SO100Her), ctypes.c_int, ctypes.c_uint64,
                                      ctypes.POINTER(SO100HerOut), _P]
+    lib.so100_replay_bytes.argtypes = []
+    lib.so100_replay_step_bytes.argtypes = []
+    lib.so100_replay_out_bytes.argtypes = []
+    lib.so100_replay_storage_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    lib.so100_replay_storage_bytes.restype = ctypes.c_int64
+    lib.so100_replay_push.argtypes = [_P, ctypes.POINTER(SO100Replay), ctypes.POINTER(SO100ReplayStep), _P]
+    lib.so100_replay_stage.argtypes = [_P, ctypes.POINTER(SO100Replay), _P, _P, _P, _P]
+    lib.so100_replay_scan.argtypes = [_P, ctypes.POINTER(SO100Replay), _P]
+    lib.so100_replay_sample.argtypes = [_P, ctypes.POINTER(SO100Replay), ctypes.c_int, ctypes.c_uint64,
+                                        ctypes.POINTER(SO100ReplayOut), _P]
     lib.so100_hull_cells.argtypes = [_P, _P, _P, ctypes.c_int]
     lib.so100_hull_blocks.argtypes = [_P, _P, ctypes.c_int]
     lib.so100_hull_support_probe.argtypes = [_P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P]
@@ -408,7 +474,9 @@ def load():
                "so100_norm_bytes", "so100_norm_ret_bytes", "so100_norm_limits", "so100_norm_work_bytes",
                "so100_norm_update", "so100_norm_apply", "so100_norm_return", "so100_her_bytes",
                "so100_her_step_bytes", "so100_her_out_bytes", "so100_her_limits", "so100_her_push",
-               "so100_her_discard", "so100_her_scan", "so100_her_sample"):
+               "so100_her_discard", "so100_her_scan", "so100_her_sample", "so100_replay_bytes",
+               "so100_replay_step_bytes", "so100_replay_out_bytes", "so100_replay_push", "so100_replay_stage",
+               "so100_replay_scan", "so100_replay_sample"):
         getattr(lib, fn).restype = ctypes.c_int
     lib.so100_struct_sizes.argtypes = [_P, _P]
     lib.so100_struct_sizes.restype = ctypes.c_int
@@ -446,7 +514,8 @@ def load():
                                  f"{ctypes.sizeof(SO100Norm)}, so100_norm_ret {lib.so100_norm_ret_bytes()} vs "
                                  f"{ctypes.sizeof(SO100NormRet)}")
     for fn, mirror in (("so100_her_bytes", SO100Her), ("so100_her_step_bytes", SO100HerStep),
-                       ("so100_her_out_bytes", SO100HerOut)):
+                       ("so100_her_out_bytes", SO100HerOut), ("so100_replay_bytes", SO100Replay),
+                       ("so100_replay_step_bytes", SO100ReplayStep), ("so100_replay_out_bytes", SO100ReplayOut)):
         if getattr(lib, fn)() != ctypes.sizeof(mirror):
             raise NativeLibraryError(f"struct layout mismatch: {fn} {getattr(lib, fn)()} vs {ctypes.sizeof(mirror)}")
     _lib = lib
@@ -483,7 +552,9 @@ EXPORTED_SYMBOLS = ("so100_abi_version", "so100_last_error", "so100_source_hash"
                     "so100_norm_bytes", "so100_norm_ret_bytes", "so100_norm_limits", "so100_norm_work_bytes",
                     "so100_norm_update", "so100_norm_apply", "so100_norm_return", "so100_her_bytes",
                     "so100_her_step_bytes", "so100_her_out_bytes", "so100_her_limits", "so100_her_storage_bytes",
-                    "so100_her_push", "so100_her_discard", "so100_her_scan", "so100_her_sample")
+                    "so100_her_push", "so100_her_discard", "so100_her_scan", "so100_her_sample", "so100_replay_bytes",
+                    "so100_replay_step_bytes", "so100_replay_out_bytes", "so100_replay_storage_bytes",
+                    "so100_replay_push", "so100_replay_stage", "so100_replay_scan", "so100_replay_sample")
 
 
 def source_hash():

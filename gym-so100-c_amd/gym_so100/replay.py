@@ -1,7 +1,11 @@
 """A hindsight replay buffer for the GoalEnv on the device: SB3 ``HerReplayBuffer``'s semantics, the
 transitions kept where the step produces them, pushed, scanned and sampled by the launches of csrc/so100_her.hip with no
 host synchronisation.  ``SO100VecEnv(replay=...)`` owns one ``HerReplay`` (``env.replay``); this module also holds the
-option checks, which touch no device."""
+option checks, which touch no device.
+
+Beside it the uniform replay buffer of the arm tasks: SB3 ``DictReplayBuffer``'s storage for state and
+pixel observations, with DrQ's random-shift augmentation in the sample launch (csrc/so100_replay.hip).
+``SO100VecEnv(uniform_replay=...)`` owns one ``UniformReplay`` (``env.uniform_replay``)."""
 import ctypes
 
 import numpy as np
@@ -185,4 +189,208 @@ class HerReplay:
             out.update(env.normalize_obs({k: out[k] for k in keys}))
             nxt = env.normalize_obs({k: out["next_" + k] for k in keys})
             out.update({"next_" + k: v for k, v in nxt.items()})
+        return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the reference's SAC("MultiInputPolicy", buffer_size=50_000, batch_size=256) on {"pixels", "agent_pos"}
+# (scripts/train_sac.py): a plain DictReplayBuffer
+UNIFORM_REPLAY_DEFAULTS = dict(buffer_size=None, augment=None, seed=None)
+AUGMENT_DEFAULT_PAD = 4          # DrQ's random shift: pad by 4, crop at a random offset
+
+
+def augment_pad(augment):
+    """The pad of an ``augment`` value: None / False -> 0 (off), True -> 4, an int -> itself, dict(pad=) -> its pad;
+    ValueError for anything else and for a pad outside 0..64."""
+    if augment is None or augment is False:
+        return 0
+    if augment is True:
+        return AUGMENT_DEFAULT_PAD
+    if isinstance(augment, dict):
+        if set(augment) != {"pad"}:
+            raise ValueError(f"uniform_replay: augment dict takes exactly the key 'pad', got {sorted(augment)}")
+        augment = augment["pad"]
+    if isinstance(augment, (bool, np.bool_)) or not isinstance(augment, (int, np.integer)):
+        raise ValueError(f"uniform_replay: augment {augment!r}: None, a bool, an int pad or dict(pad=)")
+    pad = int(augment)
+    if not 0 <= pad <= _native.SO100_REPLAY_MAX_PAD:
+        raise ValueError(f"uniform_replay: augment pad {pad} outside 0..{_native.SO100_REPLAY_MAX_PAD}")
+    return pad
+
+
+def uniform_replay_options(uniform_replay, num_envs=None, task="so100_cube_to_bin", obs_type="so100_state",
+                           autoreset=True):
+    """The checked options of ``SO100VecEnv(uniform_replay=...)`` as a dict (no device use): None -> None (off), a dict
+    -> the defaults overridden by it, with ``pad`` (the augmentation's) and, when ``num_envs`` is given, ``T =
+    buffer_size // num_envs`` (the slots per env) added.  Raises ValueError for unknown keys and bad values, and, given
+    the env's arguments, for the GoalEnv (``replay=`` is its buffer), without auto-reset, for fewer than 2 slots per env
+    and for an augmentation without pixel observations."""
+    if uniform_replay is None:
+        return None
+    if not isinstance(uniform_replay, dict):
+        raise ValueError("uniform_replay: None or a dict(" + ", ".join(f"{k}=" for k in UNIFORM_REPLAY_DEFAULTS) + ")")
+    unknown = set(uniform_replay) - set(UNIFORM_REPLAY_DEFAULTS)
+    if unknown:
+        raise ValueError(f"uniform_replay: unknown keys {sorted(unknown)}; known: {sorted(UNIFORM_REPLAY_DEFAULTS)}")
+    o = dict(UNIFORM_REPLAY_DEFAULTS)
+    o.update(uniform_replay)
+    if o["buffer_size"] is None:
+        raise ValueError("uniform_replay: buffer_size (slots over all envs) is required")
+    if isinstance(o["buffer_size"], (bool, np.bool_)) or not isinstance(o["buffer_size"], (int, np.integer)):
+        raise ValueError(f"uniform_replay: buffer_size {o['buffer_size']!r} must be an integer")
+    o["buffer_size"] = int(o["buffer_size"])
+    if o["buffer_size"] < 1:
+        raise ValueError(f"uniform_replay: buffer_size {o['buffer_size']} must be >= 1")
+    o["pad"] = augment_pad(o["augment"])
+    if o["seed"] is not None:
+        if isinstance(o["seed"], (bool, np.bool_)) or not isinstance(o["seed"], (int, np.integer)):
+            raise ValueError(f"uniform_replay: seed {o['seed']!r} must be an integer")
+        o["seed"] = int(o["seed"])
+    if num_envs is not None:
+        if task == "so100_goal":
+            raise ValueError("uniform_replay: the arm tasks' buffer; task='so100_goal' has the hindsight buffer, replay=")
+        if not autoreset:
+            raise ValueError("uniform_replay: needs autoreset=True (the step then hands over the finished episode's "
+                             "last observation and the next episode's first)")
+        T = o["buffer_size"] // int(num_envs)
+        if T < 2:
+            raise ValueError(f"uniform_replay: buffer_size {o['buffer_size']} // num_envs {num_envs} = {T} slots per "
+                             "env; a ring needs 2 (one holds the staged observation)")
+        if T * int(num_envs) >= 1 << 31:
+            raise ValueError(f"uniform_replay: {T} slots x {num_envs} envs >= 2^31")
+        if o["pad"] > 0 and obs_type != "so100_pixels_agent_pos":
+            raise ValueError("uniform_replay: augment shifts images; it needs obs_type='so100_pixels_agent_pos'")
+        o["T"] = T
+    return o
+
+
+def image_layout(shape, channels_first):
+    """(planes, H, W, chan) of an env's image tensor shape [N, ...] (include/so100.h so100_replay): [H,W,3] -> (1,H,W,3),
+    [3,H,W] -> (3,H,W,1), [K,H,W,3] -> (K,H,W,3), [K,3,H,W] -> (3K,H,W,1)"""
+    dims = tuple(int(x) for x in shape[1:])
+    if channels_first:
+        return int(np.prod(dims[:-2])), dims[-2], dims[-1], 1
+    return int(np.prod(dims[:-3])), dims[-3], dims[-2], dims[-1]
+
+
+class UniformReplay:
+    """The uniform buffer of one env (``env.uniform_replay``).  ``env.step`` pushes, ``env.reset`` stages; ``sample``
+    returns device tensors.  Every launch goes to the current stream; only ``size()`` and ``sample(check=True)`` wait for
+    the device."""
+
+    def __init__(self, env, options):
+        import torch
+        self.env, self.lib, self.o = env, env.lib, dict(options)
+        n, T, A, d = env.num_envs, int(options["T"]), env.action_dim, env.device
+        self.n, self.T, self.action_dim = n, T, A
+        self.capacity = (T - 1) * n                     # the slot at each env's cursor holds half a transition
+        self.pad = int(self.o["pad"])
+        self.seed = env.base_seed if self.o["seed"] is None else self.o["seed"] & 0xFFFFFFFFFFFFFFFF
+        self.image_shape = None if env.pixels is None else tuple(env.pixels.shape[1:])
+        layout = (0, 0, 0, 0) if env.pixels is None else image_layout(env.pixels.shape, env.channels_first)
+        self.layout = layout
+        self.P = P = int(np.prod(layout)) if env.pixels is not None else 0
+        f32, i32, u8 = torch.float32, torch.int32, torch.uint8
+        z = lambda *shape, dtype=f32: torch.zeros(*shape, dtype=dtype, device=d)  # noqa: E731
+        self.store = {"obs": z(T, n, NOBS), "next_obs": z(T, n, NOBS), "action": z(T, n, A), "reward": z(T, n),
+                      "terminated": z(T, n, dtype=u8), "meta": z(2, n, dtype=i32), "prefix": z(n + 1, dtype=i32)}
+        if P:
+            self.store["obs_img"] = z(T, n, P, dtype=u8)
+            self.store["next_img"] = z(T, n, P, dtype=u8)
+        held = sum(t.numel() * t.element_size() for t in self.store.values())
+        want = self.lib.so100_replay_storage_bytes(n, T, A, P)
+        if held != want:
+            raise RuntimeError(f"uniform_replay: the arrays hold {held} bytes, so100_replay_storage_bytes {want}")
+        self.cursor, self.count = self.store["meta"]
+        self._total = self.store["prefix"][n:]
+        self._rec = _native.SO100Replay(n=n, T=T, action_dim=A, planes=layout[0], H=layout[1], W=layout[2],
+                                        chan=layout[3], P=P, pad=0, seed=self.seed,
+                                        **{k: _native.ptr(t) for k, t in self.store.items()})
+        self._dirty = False         # a push since the last scan (host side: nothing waits for the device)
+        self.calls = 0              # sample calls so far: the draws' counter
+
+    # ------------------------------------------------------------------ the env's hooks
+    def after_reset(self, mask):
+        """the reset envs (mask: the env's uint8 mask or None = all): their fresh observation and image are staged at
+        their cursors"""
+        env = self.env
+        _native.check(self.lib.so100_replay_stage(env._handle, ctypes.byref(self._rec), _native.ptr(mask),
+                                                  _native.ptr(env.obs), _native.ptr(env.pixels), env._stream()),
+                      "so100_replay_stage")
+
+    def after_step(self, command):
+        """one transition per env from what the step left (command: the [N, action_dim] tensor ``step`` copied into)"""
+        env, P = self.env, _native.ptr
+        step = _native.SO100ReplayStep(obs=P(env.obs), final_obs=P(env.final_obs), action=P(command),
+                                       reward=P(env.reward), terminated=P(env.terminated), truncated=P(env.truncated),
+                                       diverged=P(env.diverged), pixels=P(env.pixels), final_pixels=P(env.final_pixels))
+        _native.check(self.lib.so100_replay_push(env._handle, ctypes.byref(self._rec), ctypes.byref(step),
+                                                 env._stream()), "so100_replay_push")
+        self._dirty = True
+
+    # ------------------------------------------------------------------ the user's side
+    def _scan(self):
+        if self._dirty:
+            _native.check(self.lib.so100_replay_scan(self.env._handle, ctypes.byref(self._rec), self.env._stream()),
+                          "so100_replay_scan")
+            self._dirty = False
+
+    @property
+    def valid_count(self):
+        """the transitions a sample draws from, a device int32 tensor of one element"""
+        self._scan()
+        return self._total
+
+    def size(self):
+        """``valid_count`` on the host (waits for the device)"""
+        return int(self.valid_count.item())
+
+    def sample(self, batch_size, augment=None, normalize=False, check=False):
+        """A batch of ``batch_size`` transitions as a dict of device tensors.  Pixel env: ``pixels`` / ``next_pixels``
+        ([B, *env.pixels.shape[1:]] uint8), ``agent_pos`` / ``next_agent_pos`` (columns 9:15 of the state rows) and
+        ``state`` / ``next_state`` (the 15-float rows); state env: ``obs`` / ``next_obs``.  Both: ``actions``,
+        ``rewards``, ``dones`` (terminated only), ``env``, ``slot``, ``shift`` ([B, 4]: dx, dy of the image and of the
+        next image; the pad where nothing is shifted).
+        augment: None -> the buffer's option; False -> the stored images; True, an int or dict(pad=) as in the options.
+        normalize: ``agent_pos`` (or ``obs``) and its ``next_`` twin through ``env.normalize_obs`` (ValueError without a
+        normaliser); images and rewards are never touched.  check: read ``valid_count`` and raise ValueError when it is
+        0 (an empty buffer otherwise gives rows of zeros with slot -1)."""
+        import torch
+        B = _int("batch_size", batch_size)
+        if B < 0:
+            raise ValueError(f"uniform_replay: batch_size {B} must be >= 0")
+        env = self.env
+        pad = self.pad if augment is None else augment_pad(augment)
+        if pad > 0 and not self.P:
+            raise ValueError("uniform_replay: augment shifts images; it needs obs_type='so100_pixels_agent_pos'")
+        if normalize and env._norm is None:
+            raise ValueError("uniform_replay: sample(normalize=True) needs an env built with normalize=...")
+        if check and self.size() == 0:
+            raise ValueError("uniform_replay: no transition in the buffer yet")
+        self._scan()
+        d, f32, i32 = env.device, torch.float32, torch.int32
+        e = lambda *shape, dtype=f32: torch.empty(*shape, dtype=dtype, device=d)  # noqa: E731
+        raw = {"obs": e(B, NOBS), "next_obs": e(B, NOBS), "actions": e(B, self.action_dim), "rewards": e(B),
+               "dones": e(B), "env": e(B, dtype=i32), "slot": e(B, dtype=i32), "shift": e(B, 4, dtype=i32)}
+        if self.P:
+            raw["pixels"] = e(B, *self.image_shape, dtype=torch.uint8)
+            raw["next_pixels"] = e(B, *self.image_shape, dtype=torch.uint8)
+        rec = _native.SO100ReplayOut(**{k: _native.ptr(t) for k, t in raw.items()})
+        if B:                        # (an empty tensor has no address to hand over)
+            self._rec.pad = pad
+            _native.check(self.lib.so100_replay_sample(env._handle, ctypes.byref(self._rec), B,
+                                                       ctypes.c_uint64(self.calls), ctypes.byref(rec), env._stream()),
+                          "so100_replay_sample")
+        self.calls += 1
+        if not self.P:
+            out = raw
+            if normalize:
+                out["obs"], out["next_obs"] = env.normalize_obs(out["obs"]), env.normalize_obs(out["next_obs"])
+            return out
+        out = {k: v for k, v in raw.items() if k not in ("obs", "next_obs")}
+        out["state"], out["next_state"] = raw["obs"], raw["next_obs"]
+        out["agent_pos"], out["next_agent_pos"] = raw["obs"][:, 9:15], raw["next_obs"][:, 9:15]
+        if normalize:
+            out["agent_pos"] = env.normalize_obs({"agent_pos": out["agent_pos"]})["agent_pos"]
+            out["next_agent_pos"] = env.normalize_obs({"agent_pos": out["next_agent_pos"]})["agent_pos"]
         return out

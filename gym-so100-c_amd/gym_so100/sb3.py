@@ -92,7 +92,8 @@ class SO100SB3VecEnv(_VecEnvBase):
     def __init__(self, num_envs, task="so100_cube_to_bin", device="cuda:0", seed=0, max_episode_steps=None,
                  domain_randomization=None, env_offset=0, iterations=None, solver="newton", obs_type="so100_state",
                  observation_width=640, observation_height=480, channels_first=False, cameras=None, shadows=False,
-                 antialias=False, action_mode="joint", ee_control=None, normalize=None, replay=None):
+                 antialias=False, action_mode="joint", ee_control=None, normalize=None, replay=None,
+                 uniform_replay=None):
         self.pixel_obs = obs_type == "so100_pixels_agent_pos"
         kw = {}
         self._last_obs = None                      # the observation last returned (get_original_obs: its image)
@@ -125,6 +126,8 @@ class SO100SB3VecEnv(_VecEnvBase):
             kw["normalize"] = normalize
         if replay is not None:                                     # the env's own checks (ValueError) apply
             kw["replay"] = replay
+        if uniform_replay is not None:                             # the env's own checks (ValueError) apply
+            kw["uniform_replay"] = uniform_replay
         self.venv = SO100VecEnv(num_envs, task=task, device=device, seed=seed, max_episode_steps=max_episode_steps,
                                 autoreset=True, domain_randomization=domain_randomization, env_offset=env_offset,
                                 iterations=iterations, solver=solver, episode_stats=True, **kw)
@@ -462,3 +465,53 @@ class SO100HerReplayBuffer(_ReplayBufferBase):
         return HerReplaySamples(observations={k: b[k] for k in keys}, actions=b["actions"],
                                 next_observations={k: b["next_" + k] for k in keys},
                                 dones=b["dones"].reshape(-1, 1), rewards=b["rewards"].reshape(-1, 1))
+
+
+# SB3's ReplayBufferSamples / DictReplayBufferSamples, field for field (type_aliases.py); the values are device tensors
+ReplaySamples = collections.namedtuple("ReplaySamples",
+                                       ["observations", "actions", "next_observations", "dones", "rewards"])
+
+
+class SO100ReplayBuffer(_ReplayBufferBase):
+    """The env's device-resident uniform buffer (``SO100VecEnv(uniform_replay=...)``) behind the calls
+    an SB3 off-policy learner makes on ``ReplayBuffer`` / ``DictReplayBuffer``: ``SAC(...,
+    replay_buffer_class=SO100ReplayBuffer, replay_buffer_kwargs=dict(env=env))``.  The env has stored every transition by
+    the time the learner calls ``add``, so ``add`` does nothing; ``sample`` draws (and, with ``augment``, shifts the
+    images) on the device and returns torch tensors there.  SB3's own storage is never allocated (its ``__init__`` is
+    not run)."""
+
+    def __init__(self, buffer_size=None, observation_space=None, action_space=None, env=None, device="auto", n_envs=None,
+                 **_ignored):
+        venv = getattr(env, "venv", env)
+        if venv is None or getattr(venv, "uniform_replay", None) is None:
+            raise ValueError("SO100ReplayBuffer needs env=: an SO100SB3VecEnv / SO100VecEnv built with "
+                             "uniform_replay=...")
+        self.venv, self.replay = venv, venv.uniform_replay
+        self.buffer_size = self.replay.T                     # SB3 counts slots per env
+        self.n_envs = venv.num_envs
+        self.observation_space = observation_space if observation_space is not None else \
+            getattr(env, "observation_space", None)
+        self.action_space = action_space if action_space is not None else getattr(env, "action_space", None)
+        self.device = venv.device
+        self.pos, self.full = 0, False
+
+    def add(self, *args, **kwargs):
+        """nothing: ``step`` has already pushed this transition on the device"""
+
+    def size(self):
+        """the transitions a sample draws from (waits for the device)"""
+        return self.replay.size()
+
+    def sample(self, batch_size, env=None):
+        """observations / next_observations: the dict {"pixels" [B, ...] uint8, "agent_pos" [B, 6]} of a pixel env, the
+        [B, 15] tensor of a state env, the float part normalised where the env was built with ``normalize=dict(obs=True,
+        ...)``; actions [B, A]; dones and rewards [B, 1]."""
+        norm = self.venv._norm
+        b = self.replay.sample(batch_size, normalize=norm is not None and bool(norm.out))
+        if "pixels" in b:
+            obs = {"pixels": b["pixels"], "agent_pos": b["agent_pos"]}
+            nxt = {"pixels": b["next_pixels"], "agent_pos": b["next_agent_pos"]}
+        else:
+            obs, nxt = b["obs"], b["next_obs"]
+        return ReplaySamples(observations=obs, actions=b["actions"], next_observations=nxt,
+                             dones=b["dones"].reshape(-1, 1), rewards=b["rewards"].reshape(-1, 1))

@@ -34,7 +34,7 @@ from . import _native
 from .model import NOBS, NQ, NV, build_model
 from .constants import GOAL_MAX_EPISODE_STEPS
 from .normalize import Normalizer, merge_normalize_states, normalize_options  # noqa: F401  (re-exported)
-from .replay import HerReplay, replay_options
+from .replay import HerReplay, UniformReplay, replay_options, uniform_replay_options
 
 _MAX_STEPS = {"so100_cube_to_bin": 700, "so100_touch_cube": 300, "so100_touch_cube_sparse": 300,
               "so100_goal": GOAL_MAX_EPISODE_STEPS}
@@ -282,6 +282,18 @@ class SO100VecEnv:
             resets, a diverged episode is erased, and ``replay.sample(batch_size)`` draws from the finished episodes.
             ``step_async_raw`` stores nothing.  ValueError for unknown keys and bad values, and unless
             task="so100_goal", obs_type="so100_state", autoreset=True and buffer_size // num_envs >= max_episode_steps.
+        uniform_replay: None (default: every call what it is without the argument, ``uniform_replay`` is None) or a
+            dict overriding replay.UNIFORM_REPLAY_DEFAULTS (buffer_size, augment, seed): SB3 DictReplayBuffer's storage
+            for the arm tasks, on the device (csrc/so100_replay.hip, include/so100.h so100_replay_push; DESIGN.md
+            §3.12), for both observation types.  ``buffer_size // num_envs`` slots per env, one of which holds the
+            staged observation; every ``step`` stores one transition per env (the raw 15-float observation and the true
+            next one, with pixel observations both images as ``pixels`` holds them, the command as passed in, the reward,
+            ``terminated``) with no host synchronisation, ``reset`` stages the fresh observations, a diverged step is
+            dropped, and ``uniform_replay.sample(batch_size)`` draws uniformly.  ``augment`` (None / False, True = pad 4,
+            an int pad, dict(pad=)): DrQ's random shift of the two sampled images, in the sample launch.  Depth and
+            segmentation images are not stored.  ``step_async_raw`` stores nothing.  ValueError for unknown keys and bad
+            values, for task="so100_goal" (``replay=`` is its buffer), autoreset=False, buffer_size // num_envs < 2 and
+            ``augment`` without pixel observations.
     """
 
     def __init__(self, num_envs, task="so100_cube_to_bin", obs_type="so100_state", device="cuda:0", seed=0,
@@ -289,11 +301,13 @@ class SO100VecEnv:
                  iterations=None, debug=False, solver="newton", observation_width=640, observation_height=480,
                  variant="joint", reward64=False, nsubstep=None, convex="epa", episode_stats=False, channels_first=False,
                  flat_pixels=False, depth=False, segmentation=False, cameras=None, shadows=False,
-                 antialias=False, action_mode="joint", ee_control=None, normalize=None, replay=None):
+                 antialias=False, action_mode="joint", ee_control=None, normalize=None, replay=None,
+                 uniform_replay=None):
         torch = _torch()
         norm_options = normalize_options(normalize)      # its ValueErrors before any device work
         replay_opts = replay_options(replay, num_envs, task, obs_type, autoreset,
                                      _MAX_STEPS.get(task) if max_episode_steps is None else max_episode_steps)
+        uniform_opts = uniform_replay_options(uniform_replay, num_envs, task, obs_type, autoreset)
         if norm_options is not None and norm_options["obs"] and task == "so100_goal" \
                 and obs_type == "so100_pixels_agent_pos":
             raise ValueError("normalize: the GoalEnv's flattened pixel observation ([N, 3HW+6]) is not normalised; use "
@@ -473,6 +487,7 @@ class SO100VecEnv:
             self.reward_norm = self._norm.reward_norm
             self._pre = True
         self.replay = None if replay_opts is None else HerReplay(self, replay_opts)
+        self.uniform_replay = None if uniform_opts is None else UniformReplay(self, uniform_opts)
 
     # ------------------------------------------------------------------ plumbing
     def _fill_buffers(self):
@@ -661,6 +676,8 @@ class SO100VecEnv:
             self._norm.after_reset(None if mask is None else self._mask)
         if self.replay is not None:                      # the reset envs' open episodes go, their fresh rows are staged
             self.replay.after_reset(None if mask is None else self._mask)
+        if self.uniform_replay is not None:              # the reset envs' fresh rows and images are staged
+            self.uniform_replay.after_reset(None if mask is None else self._mask)
         info = {"is_success": torch.zeros_like(self.success)}
         return self._observation(), info
 
@@ -701,6 +718,8 @@ class SO100VecEnv:
             self._norm.after_step()
         if self.replay is not None:                      # one transition per env, with the command as it came in
             self.replay.after_step(dst)
+        if self.uniform_replay is not None:
+            self.uniform_replay.after_step(dst)
         info = {"is_success": self.success, "diverged": self.diverged, "contact_bits": self.contact_bits,
                 "ncon_dropped": self.ncon_dropped}
         if self.autoreset:

@@ -700,6 +700,126 @@ int so100_her_scan(so100_env* env, const so100_her* her, void* stream);
 int so100_her_sample(so100_env* env, const so100_her* her, int batch, uint64_t call, const so100_her_out* out,
                      void* stream);
 
+/* ---- (additions to ABI 25) a uniform replay buffer for the arm tasks on the device, for state and pixel observations,
+ * with the random-shift image augmentation in the sample launch: SB3's DictReplayBuffer
+ * (scripts/train_sac.py trains SAC("MultiInputPolicy", buffer_size=50_000, batch_size=256) on {"pixels", "agent_pos"}) as
+ * launches beside the untouched step.  The caller owns every array; so100_replay names them.
+ *
+ * Storage.  A ring of T >= 2 slots for each of n envs, slot-major ([T][n][...]).  Slot s of env e holds one transition:
+ * obs (the raw 15-float observation before the step), next_obs (the true next observation: the final_obs row where the
+ * env finished, else the new obs row), action (the command given to step), reward, terminated and, with P > 0, obs_img
+ * and next_img, P = planes * H * W * chan bytes each: `planes` images of [H][W][chan] bytes.  (planes, chan) = (K, 3) for
+ * the env's HWC images of K cameras and (3 K, 1) for channels_first, so that one rule covers [H,W,3], [3,H,W], [K,H,W,3]
+ * and [K,3,H,W].  P == 0: no images, obs_img and next_img (and the image pointers of step and out) are NULL.  Both frames
+ * of a transition are stored, as DictReplayBuffer stores them.
+ * Metadata, int32 meta[2][n]: cursor[e], count[e], all zero at the start.  The slot at the cursor holds the staged
+ * "before" half (obs, obs_img) of the next transition, so the ring holds at most T - 1 complete ones: the count[e] valid
+ * transitions of env e are the slots cursor - count, .., cursor - 1 (mod T), oldest first.
+ *
+ * so100_replay_push, env e (one launch), c = cursor[e], k = count[e], done = terminated[e] | truncated[e]:
+ *   1. next_obs[c] <- done ? final_obs[e] : obs[e]; next_img[c] <- done ? final_pixels[e] : pixels[e] (the final_pixels
+ *      row of an env that is not done is never read).
+ *   2. action[c] <- action[e], reward[c] <- reward[e], terminated[c] <- terminated[e] != 0.
+ *   3. diverged[e] non-zero (diverged may be NULL): c' = c, k' = k: the transition is dropped, its slot is used again.
+ *      Else c' = (c + 1) mod T, k' = min(k + 1, T - 1).
+ *   4. obs[c'] <- obs[e], obs_img[c'] <- pixels[e]: the next transition's "before" rows (of a finished env: the new
+ *      episode's first).
+ *   5. cursor[e] <- c', count[e] <- k'.
+ *   One workgroup owns an env whole: every thread of it reads meta[e] before a workgroup barrier, thread 0 writes it after
+ *   that barrier, and no other workgroup of the launch touches meta[e] or the env's rows.
+ * so100_replay_stage: obs[cursor[e]] <- obs[e], obs_img[cursor[e]] <- pixels[e] for the envs whose mask byte is non-zero
+ *   (mask NULL = all); no count and no cursor changes (after a reset).
+ * so100_replay_scan (one launch, one workgroup; so100_her_scan's device code): prefix[e] = count[0] + .. + count[e] for
+ *   e < n, prefix[n] = the total.
+ * so100_replay_sample, batch element i (one launch; it reads prefix, so a scan must follow the last push), with
+ *   draw(field) the draw of so100_her_sample above from (seed, call, i, field):
+ *   total = prefix[n]; total == 0: every output row i is 0 (shift included), env[i] = 0, slot[i] = -1, nothing of the ring
+ *     is read.  Else
+ *   r = floor(draw(0) * total / 2^64); e = the first env with prefix[e] > r;
+ *   slot = (cursor[e] - count[e] + r - prefix[e-1]) mod T (prefix[-1] = 0): every valid transition is equally likely;
+ *   gathered: obs, next_obs, actions, rewards, dones (the stored terminated as 0 / 1), env, slot;
+ *   pad == 0: pixels <- obs_img[slot][e], next_pixels <- next_img[slot][e], byte for byte; shift[i] = (pad, pad, pad,
+ *     pad) = 0: (pad, pad) is the shift that moves nothing.
+ *   pad > 0, S = 2 pad + 1 (DrQ's random shift: replicate-pad by `pad`, crop at a random offset): the observation image
+ *     takes h = draw(2), the next image h = draw(3) (independent), dx = ((h & 0xFFFFFFFF) * S) >> 32,
+ *     dy = ((h >> 32) * S) >> 32, every plane of one image the same shift:
+ *     out[p][y][x][ch] = in[p][clamp(y + dy - pad, 0, H - 1)][clamp(x + dx - pad, 0, W - 1)][ch];
+ *     shift[i] = (dx, dy, dx', dy') (the next image's primed).
+ * Every index read from meta or prefix is clamped into its range before it addresses memory.  Byte offsets into the image
+ * arrays are 64-bit (T n P passes 2^32 at real sizes); no alignment of P or of any pointer is required. */
+#define SO100_REPLAY_MAX_ACTION 16
+#define SO100_REPLAY_MAX_PAD 64
+typedef struct so100_replay {
+  uint32_t size;            /* sizeof(so100_replay): the callee rejects a mismatch */
+  int32_t  n;               /* envs, >= 0 */
+  int32_t  T;               /* slots per env, >= 2, T * n < 2^31 */
+  int32_t  action_dim;      /* floats per command, 1..SO100_REPLAY_MAX_ACTION */
+  int32_t  planes, H, W, chan;  /* all 0 with P == 0, else all >= 1 and planes * H * W * chan == P < 2^31 */
+  int32_t  P;               /* bytes per image row, >= 0 */
+  int32_t  pad;             /* 0..SO100_REPLAY_MAX_PAD (sample; P == 0: 0) */
+  uint64_t seed;            /* (sample) */
+  float*   obs;             /* [T][n][15] */
+  float*   next_obs;        /* [T][n][15] */
+  float*   action;          /* [T][n][action_dim] */
+  float*   reward;          /* [T][n] */
+  uint8_t* terminated;      /* [T][n] */
+  uint8_t* obs_img;         /* [T][n][P], NULL with P == 0 */
+  uint8_t* next_img;        /* [T][n][P], NULL with P == 0 */
+  int32_t* meta;            /* [2][n]: cursor, count */
+  int32_t* prefix;          /* [n + 1] */
+} so100_replay;
+int so100_replay_bytes(void);
+/* The inputs of one push: device rows of the n envs, as the step left them. */
+typedef struct so100_replay_step {
+  uint32_t size;                /* sizeof(so100_replay_step) */
+  uint32_t reserved0;
+  const float*   obs;           /* [n][15] */
+  const float*   final_obs;     /* [n][15]: read where terminated | truncated */
+  const float*   action;        /* [n][action_dim] */
+  const float*   reward;        /* [n] */
+  const uint8_t* terminated;    /* [n] */
+  const uint8_t* truncated;     /* [n] */
+  const uint8_t* diverged;      /* [n] or NULL */
+  const uint8_t* pixels;        /* [n][P], NULL with P == 0 */
+  const uint8_t* final_pixels;  /* [n][P]: read where terminated | truncated; NULL with P == 0 */
+} so100_replay_step;
+int so100_replay_step_bytes(void);
+/* The outputs of one sample call: device arrays of `batch` rows. */
+typedef struct so100_replay_out {
+  uint32_t size;              /* sizeof(so100_replay_out) */
+  uint32_t reserved0;
+  float*   obs;               /* [B][15] */
+  float*   next_obs;          /* [B][15] */
+  float*   actions;           /* [B][action_dim] */
+  float*   rewards;           /* [B] */
+  float*   dones;             /* [B] */
+  uint8_t* pixels;            /* [B][P], NULL with P == 0 */
+  uint8_t* next_pixels;       /* [B][P], NULL with P == 0 */
+  int32_t* env;               /* [B] */
+  int32_t* slot;              /* [B] */
+  int32_t* shift;             /* [B][4] */
+} so100_replay_out;
+int so100_replay_out_bytes(void);
+/* Bytes of all the arrays of so100_replay together: T n (4 (15 + 15 + action_dim + 1) + 1 + 2 P) + 4 (2 n + n + 1), in
+ * 64-bit arithmetic; -1 (text in so100_last_error) for n < 0, T < 2, T * n >= 2^31, an action_dim outside
+ * 1..SO100_REPLAY_MAX_ACTION or P < 0. */
+int64_t so100_replay_storage_bytes(int n, int T, int action_dim, int P);
+/* All four: launches on `stream` (one each), no allocation, no synchronisation, no atomics; push and stage launch nothing
+ * for n = 0, sample nothing for batch = 0.  Nonzero (text in so100_last_error) before any device work and with nothing
+ * written, in this order: NULL replay, a wrong `size`, T < 2, n < 0, T * n >= 2^31, an action_dim outside
+ * 1..SO100_REPLAY_MAX_ACTION, inconsistent planes / H / W / chan / P (P < 0; P == 0 with one of the four non-zero; P > 0
+ * with one of them < 1 or their product not P), a pad outside 0..SO100_REPLAY_MAX_PAD or non-zero with P == 0, (sample)
+ * batch < 0, NULL out or a wrong `size` of it, (push) NULL step or a wrong `size` of it; then a NULL env, a NULL required
+ * array of so100_replay, image arrays of so100_replay present with P == 0 or absent with P > 0, a NULL required pointer of
+ * step or out, image pointers of step or out present with P == 0 or absent with P > 0, (stage) the same for obs and
+ * pixels. */
+int so100_replay_push(so100_env* env, const so100_replay* replay, const so100_replay_step* step, void* stream);
+int so100_replay_stage(so100_env* env, const so100_replay* replay, const uint8_t* mask /* [n] or NULL */,
+                       const float* obs /* [n][15] */, const uint8_t* pixels /* [n][P], NULL with P == 0 */, void* stream);
+int so100_replay_scan(so100_env* env, const so100_replay* replay, void* stream);
+int so100_replay_sample(so100_env* env, const so100_replay* replay, int batch, uint64_t call, const so100_replay_out* out,
+                        void* stream);
+
 /* Batched sparse GoalEnv reward (env.py:341-353): out[i] = ||a_i - d_i|| < threshold ? 0 : -1. */
 int so100_goal_reward(so100_env* env, int n, const float* achieved, const float* desired, float* out,
                       void* stream);
