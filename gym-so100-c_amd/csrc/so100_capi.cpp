@@ -81,6 +81,11 @@ hipError_t launch_replay_push(const so100_replay&, const so100_replay_step&, hip
 hipError_t launch_replay_stage(const so100_replay&, const uint8_t*, const float*, const uint8_t*, hipStream_t);
 hipError_t launch_replay_scan(const so100_replay&, hipStream_t);
 hipError_t launch_replay_sample(const so100_replay&, const so100_replay_out&, int, uint64_t, hipStream_t);
+hipError_t launch_replay_push_nstep(const so100_replay&, const so100_replay_nstep&, const so100_replay_step&, hipStream_t);
+hipError_t launch_replay_stage_nstep(const so100_replay&, const so100_replay_nstep&, const uint8_t*, const float*,
+                                     const uint8_t*, hipStream_t);
+hipError_t launch_replay_sample_nstep(const so100_replay&, const so100_replay_out&, const so100_replay_nstep&,
+                                      const so100_replay_nstep_out&, int, uint64_t, hipStream_t);
 }  // namespace so100
 
 using so100::DevModel;
@@ -1828,13 +1833,34 @@ static int replay_check_ptrs(const char* fn, const so100_env* env, const so100_r
   return 0;
 }
 
-static int so100_replay_push_impl(so100_env* env, const so100_replay* h, const so100_replay_step* st, void* stream) {
-  const char* fn = "so100_replay_push";
+// the n-step record's numbers (include/so100.h: after the call's own records, before the env) and its array (after
+// so100_replay's)
+static int replay_check_nstep(const char* fn, const so100_replay* h, const so100_replay_nstep* ns) {
+  if (!ns) return her_fail(fn, "NULL nstep");
+  if (ns->size != sizeof(so100_replay_nstep))
+    return size_mismatch(fn, "so100_replay_nstep", ns->size, sizeof(so100_replay_nstep));
+  const int most = h->T - 1 < SO100_REPLAY_MAX_NSTEP ? h->T - 1 : SO100_REPLAY_MAX_NSTEP;
+  if (ns->n_step < 1 || ns->n_step > most) return her_fail(fn, "n_step outside 1..min(16, T - 1)");
+  if (!(ns->gamma >= 0.f && ns->gamma <= 1.f)) return her_fail(fn, "gamma outside [0, 1]");      // false for NaN
+  return 0;
+}
+static int replay_check_ends(const char* fn, const so100_replay_nstep* ns) {
+  return ns->ends ? 0 : her_fail(fn, "NULL ends in so100_replay_nstep");
+}
+
+// nstep: the _nstep entry point (ns is then checked), else ns is not looked at
+static int so100_replay_push_impl(so100_env* env, const so100_replay* h, const so100_replay_nstep* ns, bool nstep,
+                                  const so100_replay_step* st, void* stream) {
+  const char* fn = nstep ? "so100_replay_push_nstep" : "so100_replay_push";
   if (int rc = replay_check(fn, h)) return rc;
   if (!st) return her_fail(fn, "NULL step");
   if (st->size != sizeof(so100_replay_step))
     return size_mismatch(fn, "so100_replay_step", st->size, sizeof(so100_replay_step));
+  if (nstep)
+    if (int rc = replay_check_nstep(fn, h, ns)) return rc;
   if (int rc = replay_check_ptrs(fn, env, h)) return rc;
+  if (nstep)
+    if (int rc = replay_check_ends(fn, ns)) return rc;
   if (!st->obs || !st->final_obs || !st->action || !st->reward || !st->terminated || !st->truncated)
     return her_fail(fn, "NULL pointer in so100_replay_step");
   if (h->P == 0 && (st->pixels || st->final_pixels)) return her_fail(fn, "image pointers in so100_replay_step with P == 0");
@@ -1842,21 +1868,27 @@ static int so100_replay_push_impl(so100_env* env, const so100_replay* h, const s
     return her_fail(fn, "NULL image pointer in so100_replay_step with P > 0");
   if (h->n == 0) return 0;
   DeviceGuard g(env->device);
-  hipError_t e = so100::launch_replay_push(*h, *st, (hipStream_t)stream);
+  hipError_t e = nstep ? so100::launch_replay_push_nstep(*h, *ns, *st, (hipStream_t)stream)
+                       : so100::launch_replay_push(*h, *st, (hipStream_t)stream);
   return e == hipSuccess ? 0 : fail_hip(fn, e);
 }
 
-static int so100_replay_stage_impl(so100_env* env, const so100_replay* h, const uint8_t* mask, const float* obs,
-                                   const uint8_t* pixels, void* stream) {
-  const char* fn = "so100_replay_stage";
+static int so100_replay_stage_impl(so100_env* env, const so100_replay* h, const so100_replay_nstep* ns, bool nstep,
+                                   const uint8_t* mask, const float* obs, const uint8_t* pixels, void* stream) {
+  const char* fn = nstep ? "so100_replay_stage_nstep" : "so100_replay_stage";
   if (int rc = replay_check(fn, h)) return rc;
+  if (nstep)
+    if (int rc = replay_check_nstep(fn, h, ns)) return rc;
   if (int rc = replay_check_ptrs(fn, env, h)) return rc;
+  if (nstep)
+    if (int rc = replay_check_ends(fn, ns)) return rc;
   if (!obs) return her_fail(fn, "NULL obs");
   if (h->P == 0 && pixels) return her_fail(fn, "pixels with P == 0");
   if (h->P > 0 && !pixels) return her_fail(fn, "NULL pixels with P > 0");
   if (h->n == 0) return 0;
   DeviceGuard g(env->device);
-  hipError_t e = so100::launch_replay_stage(*h, mask, obs, pixels, (hipStream_t)stream);
+  hipError_t e = nstep ? so100::launch_replay_stage_nstep(*h, *ns, mask, obs, pixels, (hipStream_t)stream)
+                       : so100::launch_replay_stage(*h, mask, obs, pixels, (hipStream_t)stream);
   return e == hipSuccess ? 0 : fail_hip(fn, e);
 }
 
@@ -1869,22 +1901,34 @@ static int so100_replay_scan_impl(so100_env* env, const so100_replay* h, void* s
   return e == hipSuccess ? 0 : fail_hip(fn, e);
 }
 
-static int so100_replay_sample_impl(so100_env* env, const so100_replay* h, int batch, uint64_t call,
-                                    const so100_replay_out* o, void* stream) {
-  const char* fn = "so100_replay_sample";
+static int so100_replay_sample_impl(so100_env* env, const so100_replay* h, const so100_replay_nstep* ns, bool nstep,
+                                    int batch, uint64_t call, const so100_replay_out* o,
+                                    const so100_replay_nstep_out* no, void* stream) {
+  const char* fn = nstep ? "so100_replay_sample_nstep" : "so100_replay_sample";
   if (int rc = replay_check(fn, h)) return rc;
   if (batch < 0) return her_fail(fn, "batch < 0");
   if (!o) return her_fail(fn, "NULL out");
   if (o->size != sizeof(so100_replay_out)) return size_mismatch(fn, "so100_replay_out", o->size, sizeof(so100_replay_out));
+  if (nstep) {
+    if (int rc = replay_check_nstep(fn, h, ns)) return rc;
+    if (!no) return her_fail(fn, "NULL nout");
+    if (no->size != sizeof(so100_replay_nstep_out))
+      return size_mismatch(fn, "so100_replay_nstep_out", no->size, sizeof(so100_replay_nstep_out));
+  }
   if (int rc = replay_check_ptrs(fn, env, h)) return rc;
+  if (nstep)
+    if (int rc = replay_check_ends(fn, ns)) return rc;
   if (!o->obs || !o->next_obs || !o->actions || !o->rewards || !o->dones || !o->env || !o->slot || !o->shift)
     return her_fail(fn, "NULL pointer in so100_replay_out");
   if (h->P == 0 && (o->pixels || o->next_pixels)) return her_fail(fn, "image pointers in so100_replay_out with P == 0");
   if (h->P > 0 && (!o->pixels || !o->next_pixels))
     return her_fail(fn, "NULL image pointer in so100_replay_out with P > 0");
+  if (nstep && (!no->discounts || !no->nsteps || !no->last_slot))
+    return her_fail(fn, "NULL pointer in so100_replay_nstep_out");
   if (batch == 0) return 0;
   DeviceGuard g(env->device);
-  hipError_t e = so100::launch_replay_sample(*h, *o, batch, call, (hipStream_t)stream);
+  hipError_t e = nstep ? so100::launch_replay_sample_nstep(*h, *o, *ns, *no, batch, call, (hipStream_t)stream)
+                       : so100::launch_replay_sample(*h, *o, batch, call, (hipStream_t)stream);
   return e == hipSuccess ? 0 : fail_hip(fn, e);
 }
 
@@ -2031,7 +2075,7 @@ int64_t so100_replay_storage_bytes(int n, int T, int action_dim, int P) {
 
 int so100_replay_push(so100_env* env, const so100_replay* replay, const so100_replay_step* step, void* stream) {
   try {
-    return so100_replay_push_impl(env, replay, step, stream);
+    return so100_replay_push_impl(env, replay, nullptr, false, step, stream);
   } catch (...) {
     return caught("so100_replay_push");
   }
@@ -2040,7 +2084,7 @@ int so100_replay_push(so100_env* env, const so100_replay* replay, const so100_re
 int so100_replay_stage(so100_env* env, const so100_replay* replay, const uint8_t* mask, const float* obs,
                        const uint8_t* pixels, void* stream) {
   try {
-    return so100_replay_stage_impl(env, replay, mask, obs, pixels, stream);
+    return so100_replay_stage_impl(env, replay, nullptr, false, mask, obs, pixels, stream);
   } catch (...) {
     return caught("so100_replay_stage");
   }
@@ -2057,9 +2101,48 @@ int so100_replay_scan(so100_env* env, const so100_replay* replay, void* stream) 
 int so100_replay_sample(so100_env* env, const so100_replay* replay, int batch, uint64_t call, const so100_replay_out* out,
                         void* stream) {
   try {
-    return so100_replay_sample_impl(env, replay, batch, call, out, stream);
+    return so100_replay_sample_impl(env, replay, nullptr, false, batch, call, out, nullptr, stream);
   } catch (...) {
     return caught("so100_replay_sample");
+  }
+}
+
+int so100_replay_nstep_bytes(void) { return (int)sizeof(so100_replay_nstep); }
+int so100_replay_nstep_out_bytes(void) { return (int)sizeof(so100_replay_nstep_out); }
+
+int64_t so100_replay_nstep_storage_bytes(int n, int T) {
+  if (n < 0 || T < 2 || (long long)T * n >= (1ll << 31)) {
+    fail("so100_replay_nstep_storage_bytes: n < 0, T < 2 or T * n >= 2^31");
+    return -1;
+  }
+  return (int64_t)T * n;
+}
+
+int so100_replay_push_nstep(so100_env* env, const so100_replay* replay, const so100_replay_nstep* nstep,
+                            const so100_replay_step* step, void* stream) {
+  try {
+    return so100_replay_push_impl(env, replay, nstep, true, step, stream);
+  } catch (...) {
+    return caught("so100_replay_push_nstep");
+  }
+}
+
+int so100_replay_stage_nstep(so100_env* env, const so100_replay* replay, const so100_replay_nstep* nstep,
+                             const uint8_t* mask, const float* obs, const uint8_t* pixels, void* stream) {
+  try {
+    return so100_replay_stage_impl(env, replay, nstep, true, mask, obs, pixels, stream);
+  } catch (...) {
+    return caught("so100_replay_stage_nstep");
+  }
+}
+
+int so100_replay_sample_nstep(so100_env* env, const so100_replay* replay, const so100_replay_nstep* nstep, int batch,
+                              uint64_t call, const so100_replay_out* out, const so100_replay_nstep_out* nout,
+                              void* stream) {
+  try {
+    return so100_replay_sample_impl(env, replay, nstep, true, batch, call, out, nout, stream);
+  } catch (...) {
+    return caught("so100_replay_sample_nstep");
   }
 }
 

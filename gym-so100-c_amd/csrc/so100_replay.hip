@@ -29,6 +29,11 @@
 // pad == 0 by the aligned join above, with pad > 0 from 4 byte loads at the clamped source coordinates, found by two
 // divisions per word and increments between its bytes.  The stores are contiguous 256-byte runs per wave; the loads are
 // rows of the ring, each source byte fetched from HBM once and again only from L1 / L2.
+//
+// N-step returns (so100_replay_push_nstep, so100_replay_stage_nstep, so100_replay_sample_nstep).  The
+// same three kernel bodies, instantiated a second time with the `ends` bytes: push and stage mark where an episode ends,
+// the sample reads the window's n_step `ends` bytes and rewards in one round (one slot per lane), finds its length by a
+// ballot and sums the rewards in a fixed order by shuffles.  The plain entry points launch the instantiations without.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "so100.h"
@@ -103,6 +108,7 @@ __device__ __forceinline__ void copy_row(uint8_t* dst, uint8_t* dst2, const uint
 
 struct RepPick {
   int e, slot;
+  int k, cnt;                                            // the slot's index among the env's valid transitions, their count
   bool any;
 };
 
@@ -143,7 +149,7 @@ __device__ __forceinline__ int find_env_wave(const int32_t* prefix, int n, long 
 // whole waves with one i per wave
 template <bool WAVE>
 __device__ __forceinline__ RepPick replay_pick(const so100_replay& h, uint64_t call, size_t i) {
-  RepPick p = {0, -1, false};
+  RepPick p = {0, -1, 0, 0, false};
   const int n = h.n, T = h.T;
   const long long cap = (long long)(T - 1) * n;
   long long total = h.prefix[n];
@@ -158,6 +164,8 @@ __device__ __forceinline__ RepPick replay_pick(const so100_replay& h, uint64_t c
   const int cnt = clampi(h.meta[(size_t)n + e], 0, T - 1);
   p.e = e;
   p.slot = add_mod(sub_mod(cur, cnt, T), k, T);
+  p.k = k;
+  p.cnt = cnt;
   p.any = true;
   return p;
 }
@@ -199,9 +207,27 @@ struct RepCoord {
   }
 };
 
-}  // namespace
+// the length m of the n-step window that starts at the pick p (so100_replay_sample_nstep, rule 2), by the lanes
+// [base, base + 16) of a wave, all of them active and with the same p: lane base + j looks at the window's slot j (its
+// `ends` byte, `closes`, and whether it is the env's newest transition), a ballot finds the first that stops the window.
+// n_step <= 16, and lane base + n_step - 1 always stops it, so 1 <= m <= n_step
+__device__ __forceinline__ int window_length(bool closes, int j, const RepPick& p, int n_step, int base) {
+  const bool stop = j < n_step && (j + 1 == n_step || closes || p.k + j + 1 >= p.cnt);
+  const unsigned long long b = __ballot(stop) >> base;
+  return __ffs((unsigned)(b & 0xFFFFull));               // (0 only if n_step < 1, which the launcher refuses)
+}
 
-__global__ __launch_bounds__(kRepThreads) void so100_replay_push_kernel(so100_replay h, so100_replay_step s) {
+// acc + g r in float32 with the product rounded before the sum (so100_replay_sample_nstep, rule 3).  Written out under
+// the pragma: to the compiler __fmul_rn and __fadd_rn are a plain * and +, which it contracts into one fused multiply-add
+__device__ __forceinline__ float mul_then_add(float acc, float g, float r) {
+#pragma clang fp contract(off)
+  const float p = g * r;
+  return acc + p;
+}
+
+// NSTEP: with the `ends` bytes (rules 6 and 7 of so100_replay_push_nstep); ends is NULL otherwise
+template <bool NSTEP>
+__device__ __forceinline__ void replay_push_body(const so100_replay& h, const so100_replay_step& s, uint8_t* ends) {
   const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
   const int e = (int)blockIdx.x, n = h.n, T = h.T, A = h.action_dim, P = h.P;
   const int c = clampi(h.meta[e], 0, T - 1);
@@ -221,6 +247,10 @@ __global__ __launch_bounds__(kRepThreads) void so100_replay_push_kernel(so100_re
   if (tid == 32) {
     h.reward[row] = s.reward[e];
     h.terminated[row] = s.terminated[e] != 0 ? 1 : 0;
+    if (NSTEP) {
+      ends[row] = done ? 1 : 0;                          // 6.
+      if (drop && k > 0) ends[(size_t)sub_mod(c, 1, T) * n + e] = 1;   // 7.
+    }
   }
   if (P > 0) {
     const uint8_t* now = s.pixels + (size_t)e * P;
@@ -240,21 +270,58 @@ __global__ __launch_bounds__(kRepThreads) void so100_replay_push_kernel(so100_re
   }
 }
 
-__global__ __launch_bounds__(kRepThreads) void so100_replay_stage_kernel(so100_replay h, const uint8_t* __restrict__ mask,
-                                                                         const float* __restrict__ obs,
-                                                                         const uint8_t* __restrict__ pixels) {
+}  // namespace
+
+__global__ __launch_bounds__(kRepThreads) void so100_replay_push_kernel(so100_replay h, so100_replay_step s) {
+  replay_push_body<false>(h, s, nullptr);
+}
+
+__global__ __launch_bounds__(kRepThreads) void so100_replay_push_nstep_kernel(so100_replay h, so100_replay_step s,
+                                                                               uint8_t* ends) {
+  replay_push_body<true>(h, s, ends);
+}
+
+namespace {
+
+template <bool NSTEP>
+__device__ __forceinline__ void replay_stage_body(const so100_replay& h, const uint8_t* __restrict__ mask,
+                                                  const float* __restrict__ obs, const uint8_t* __restrict__ pixels,
+                                                  uint8_t* ends) {
   const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
   const int e = (int)blockIdx.x, n = h.n, T = h.T, P = h.P;
   if (mask != nullptr && mask[e] == 0) return;
   const int c = clampi(h.meta[e], 0, T - 1);
   const size_t row = (size_t)c * n + e;
   if (tid < kRepObs) h.obs[row * kRepObs + tid] = obs[(size_t)e * kRepObs + tid];
+  if (NSTEP && tid == 32 && clampi(h.meta[(size_t)n + e], 0, T - 1) > 0) ends[(size_t)sub_mod(c, 1, T) * n + e] = 1;
   if (P > 0) copy_row<false>(h.obs_img + row * P, nullptr, pixels + (size_t)e * P, P, tid, nt);
 }
 
-__global__ __launch_bounds__(kRepThreads) void so100_replay_sample_kernel(so100_replay h, so100_replay_out o, int batch,
-                                                                          uint64_t call, unsigned row_groups, int chunks,
-                                                                          int span) {
+}  // namespace
+
+__global__ __launch_bounds__(kRepThreads) void so100_replay_stage_kernel(so100_replay h, const uint8_t* __restrict__ mask,
+                                                                         const float* __restrict__ obs,
+                                                                         const uint8_t* __restrict__ pixels) {
+  replay_stage_body<false>(h, mask, obs, pixels, nullptr);
+}
+
+__global__ __launch_bounds__(kRepThreads) void so100_replay_stage_nstep_kernel(so100_replay h,
+                                                                                const uint8_t* __restrict__ mask,
+                                                                                const float* __restrict__ obs,
+                                                                                const uint8_t* __restrict__ pixels,
+                                                                                uint8_t* ends) {
+  replay_stage_body<true>(h, mask, obs, pixels, ends);
+}
+
+namespace {
+
+// NSTEP: with the n-step window (so100_replay_sample_nstep); ns and no are not read otherwise.  The window adds one round
+// of loads to the chain that a workgroup pays before its first byte moves, whatever n_step is: the addresses of the
+// window's `ends` and reward entries follow from the pick, so the lanes read them side by side.
+template <bool NSTEP>
+__device__ __forceinline__ void replay_sample_body(const so100_replay& h, const so100_replay_out& o,
+                                                   const so100_replay_nstep& ns, const so100_replay_nstep_out& no,
+                                                   int batch, uint64_t call, unsigned row_groups, int chunks, int span) {
   const int n = h.n, A = h.action_dim, P = h.P, pad = h.pad;
   if (blockIdx.x < row_groups) {
     // ---- the float rows, 16 lanes per batch element
@@ -276,13 +343,42 @@ __global__ __launch_bounds__(kRepThreads) void so100_replay_sample_kernel(so100_
         o.dones[i] = 0.f;
         o.env[i] = 0;
         o.slot[i] = -1;
+        if (NSTEP) {
+          no.discounts[i] = 0.f;
+          no.nsteps[i] = 0;
+          no.last_slot[i] = -1;
+        }
       }
       return;
     }
     const size_t row = (size_t)p.slot * n + p.e;
+    size_t last = row;                                   // the row of the window's last transition
+    float ret = 0.f, disc = 0.f;
+    int m = 1, last_slot = p.slot;
+    if (NSTEP) {
+      // lane j of the element's 16: ends and reward of the window's slot j, in one round
+      const int T = h.T;
+      const bool mine = c < ns.n_step;
+      const size_t wrow = (size_t)add_mod(p.slot, mine ? c : 0, T) * n + p.e;
+      const bool closes = mine && ns.ends[wrow] != 0;
+      const float rw = mine ? h.reward[wrow] : 0.f;
+      m = clampi(window_length(closes, c, p, ns.n_step, (int)threadIdx.x & 48), 1, ns.n_step);
+      // every lane sums in the header's order: each product rounded, then each sum
+      ret = __shfl(rw, 0, kRepLanes);
+      disc = ns.gamma;
+      for (int j = 1; j < ns.n_step; j++) {
+        const float rj = __shfl(rw, j, kRepLanes);
+        if (j < m) {
+          ret = mul_then_add(ret, disc, rj);
+          disc = disc * ns.gamma;
+        }
+      }
+      last_slot = add_mod(p.slot, m - 1, T);
+      last = (size_t)last_slot * n + p.e;
+    }
     if (c < kRepObs) {
       o.obs[i * kRepObs + c] = h.obs[row * kRepObs + c];
-      o.next_obs[i * kRepObs + c] = h.next_obs[row * kRepObs + c];
+      o.next_obs[i * kRepObs + c] = h.next_obs[last * kRepObs + c];
     }
     if (c < A) o.actions[i * A + c] = h.action[row * A + c];
     if (c < 4) {
@@ -294,10 +390,15 @@ __global__ __launch_bounds__(kRepThreads) void so100_replay_sample_kernel(so100_
       o.shift[i * 4 + c] = c == 0 ? d[0] : (c == 1 ? d[1] : (c == 2 ? d[2] : d[3]));
     }
     if (!scalar) return;
-    o.rewards[i] = h.reward[row];
-    o.dones[i] = h.terminated[row] != 0 ? 1.f : 0.f;
+    o.rewards[i] = NSTEP ? ret : h.reward[row];
+    o.dones[i] = h.terminated[last] != 0 ? 1.f : 0.f;
     o.env[i] = p.e;
     o.slot[i] = p.slot;
+    if (NSTEP) {
+      no.discounts[i] = disc;
+      no.nsteps[i] = m;
+      no.last_slot[i] = last_slot;
+    }
     return;
   }
   // ---- the images: a piece is `span` chunks of kChunk bytes of one output image
@@ -331,7 +432,15 @@ __global__ __launch_bounds__(kRepThreads) void so100_replay_sample_kernel(so100_
       }
       continue;
     }
-    const uint8_t* src = (which ? h.next_img : h.obs_img) + ((size_t)p.slot * n + p.e) * (size_t)P;
+    int slot = p.slot;
+    if (NSTEP && which) {                                // the next image is the window's last: lane j of each wave
+      const int lane = tid & 63, T = h.T;                // reads the `ends` byte of the window's slot j
+      const bool mine = lane < ns.n_step;
+      const bool closes = mine && ns.ends[(size_t)add_mod(p.slot, mine ? lane : 0, T) * n + p.e] != 0;
+      const int m = clampi(window_length(closes, lane, p, ns.n_step, 0), 1, ns.n_step);
+      slot = add_mod(p.slot, m - 1, T);
+    }
+    const uint8_t* src = (which ? h.next_img : h.obs_img) + ((size_t)slot * n + p.e) * (size_t)P;
     if (pad == 0) {
       if (ends && tid < head) dst[tid] = src[tid];
       if (ends && tail0 + tid < P) dst[tail0 + tid] = src[tail0 + tid];
@@ -375,6 +484,22 @@ __global__ __launch_bounds__(kRepThreads) void so100_replay_sample_kernel(so100_
   }
 }
 
+}  // namespace
+
+__global__ __launch_bounds__(kRepThreads) void so100_replay_sample_kernel(so100_replay h, so100_replay_out o, int batch,
+                                                                          uint64_t call, unsigned row_groups, int chunks,
+                                                                          int span) {
+  replay_sample_body<false>(h, o, so100_replay_nstep{}, so100_replay_nstep_out{}, batch, call, row_groups, chunks, span);
+}
+
+__global__ __launch_bounds__(kRepThreads) void so100_replay_sample_nstep_kernel(so100_replay h, so100_replay_out o,
+                                                                                so100_replay_nstep ns,
+                                                                                so100_replay_nstep_out no, int batch,
+                                                                                uint64_t call, unsigned row_groups,
+                                                                                int chunks, int span) {
+  replay_sample_body<true>(h, o, ns, no, batch, call, row_groups, chunks, span);
+}
+
 hipError_t launch_replay_push(const so100_replay& h, const so100_replay_step& st, hipStream_t s) {
   hipLaunchKernelGGL(so100_replay_push_kernel, dim3((unsigned)h.n), dim3(h.P > 0 ? kRepThreads : kRepStateThreads), 0, s,
                      h, st);
@@ -392,8 +517,9 @@ hipError_t launch_replay_scan(const so100_replay& h, hipStream_t s) {
   return launch_count_scan(h.n, h.T - 1, h.meta + h.n, h.prefix, s);
 }
 
-hipError_t launch_replay_sample(const so100_replay& h, const so100_replay_out& o, int batch, uint64_t call,
-                                hipStream_t s) {
+// ns, no: NULL for the plain sample
+static hipError_t launch_sample(const so100_replay& h, const so100_replay_out& o, const so100_replay_nstep* ns,
+                                const so100_replay_nstep_out* no, int batch, uint64_t call, hipStream_t s) {
   const unsigned row_groups = (unsigned)(((long long)batch + kRepRows - 1) / kRepRows);
   const int chunks = (h.P + kChunk - 1) / kChunk;        // 0 without images
   // a workgroup finds its row's transition once (the draw, a search of the prefix sums, the metadata: dependent loads),
@@ -403,8 +529,36 @@ hipError_t launch_replay_sample(const so100_replay& h, const so100_replay_out& o
   span = span < 1 ? 1 : (span > chunks ? chunks : span);
   const long long pieces = chunks > 0 ? 2ll * ((chunks + span - 1) / span) * batch : 0;
   const unsigned piece_groups = (unsigned)(pieces < (long long)kMaxPieceGroups ? pieces : (long long)kMaxPieceGroups);
-  hipLaunchKernelGGL(so100_replay_sample_kernel, dim3(row_groups + piece_groups), dim3(kRepThreads), 0, s, h, o, batch,
-                     call, row_groups, chunks, (int)span);
+  if (ns != nullptr)
+    hipLaunchKernelGGL(so100_replay_sample_nstep_kernel, dim3(row_groups + piece_groups), dim3(kRepThreads), 0, s, h, o,
+                       *ns, *no, batch, call, row_groups, chunks, (int)span);
+  else
+    hipLaunchKernelGGL(so100_replay_sample_kernel, dim3(row_groups + piece_groups), dim3(kRepThreads), 0, s, h, o, batch,
+                       call, row_groups, chunks, (int)span);
+  return hipGetLastError();
+}
+
+hipError_t launch_replay_sample(const so100_replay& h, const so100_replay_out& o, int batch, uint64_t call,
+                                hipStream_t s) {
+  return launch_sample(h, o, nullptr, nullptr, batch, call, s);
+}
+
+hipError_t launch_replay_sample_nstep(const so100_replay& h, const so100_replay_out& o, const so100_replay_nstep& ns,
+                                      const so100_replay_nstep_out& no, int batch, uint64_t call, hipStream_t s) {
+  return launch_sample(h, o, &ns, &no, batch, call, s);
+}
+
+hipError_t launch_replay_push_nstep(const so100_replay& h, const so100_replay_nstep& ns, const so100_replay_step& st,
+                                    hipStream_t s) {
+  hipLaunchKernelGGL(so100_replay_push_nstep_kernel, dim3((unsigned)h.n), dim3(h.P > 0 ? kRepThreads : kRepStateThreads),
+                     0, s, h, st, ns.ends);
+  return hipGetLastError();
+}
+
+hipError_t launch_replay_stage_nstep(const so100_replay& h, const so100_replay_nstep& ns, const uint8_t* mask,
+                                     const float* obs, const uint8_t* pixels, hipStream_t s) {
+  hipLaunchKernelGGL(so100_replay_stage_nstep_kernel, dim3((unsigned)h.n),
+                     dim3(h.P > 0 ? kRepThreads : kRepStateThreads), 0, s, h, mask, obs, pixels, ns.ends);
   return hipGetLastError();
 }
 

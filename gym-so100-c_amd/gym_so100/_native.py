@@ -312,6 +312,36 @@ class SO100ReplayOut(ctypes.Structure):
             setattr(self, name, p)
 
 
+SO100_REPLAY_MAX_NSTEP = 16       # include/so100.h
+REPLAY_NSTEP_OUTPUTS = ("discounts", "nsteps", "last_slot")
+
+
+class SO100ReplayNstep(ctypes.Structure):
+    """Mirror of ``so100_replay_nstep`` (include/so100.h): the window of an n-step sample and the ``ends`` array that the
+    ``_nstep`` push and stage keep."""
+    _fields_ = [("size", ctypes.c_uint32), ("n_step", ctypes.c_int32), ("gamma", ctypes.c_float),
+                ("reserved0", ctypes.c_uint32), ("ends", _P)]
+
+    def __init__(self, n_step=1, gamma=0.99, ends=None):
+        super().__init__()
+        self.size = ctypes.sizeof(SO100ReplayNstep)
+        self.n_step, self.gamma, self.ends = int(n_step), float(gamma), ends
+
+
+class SO100ReplayNstepOut(ctypes.Structure):
+    """Mirror of ``so100_replay_nstep_out`` (include/so100.h): the device arrays one ``so100_replay_sample_nstep`` fills
+    beside those of ``so100_replay_out``."""
+    _fields_ = [("size", ctypes.c_uint32), ("reserved0", ctypes.c_uint32)] + [(name, _P) for name in REPLAY_NSTEP_OUTPUTS]
+
+    def __init__(self, **outputs):
+        super().__init__()
+        self.size = ctypes.sizeof(SO100ReplayNstepOut)
+        for name, p in outputs.items():
+            if name not in REPLAY_NSTEP_OUTPUTS:
+                raise TypeError(f"so100_replay_nstep_out has no output {name!r}")
+            setattr(self, name, p)
+
+
 SO100_NMATERIAL = 5
 
 
@@ -450,6 +480,17 @@ def load():
     lib.so100_replay_scan.argtypes = [_P, ctypes.POINTER(SO100Replay), _P]
     lib.so100_replay_sample.argtypes = [_P, ctypes.POINTER(SO100Replay), ctypes.c_int, ctypes.c_uint64,
                                         ctypes.POINTER(SO100ReplayOut), _P]
+    lib.so100_replay_nstep_bytes.argtypes = []
+    lib.so100_replay_nstep_out_bytes.argtypes = []
+    lib.so100_replay_nstep_storage_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+    lib.so100_replay_nstep_storage_bytes.restype = ctypes.c_int64
+    lib.so100_replay_push_nstep.argtypes = [_P, ctypes.POINTER(SO100Replay), ctypes.POINTER(SO100ReplayNstep),
+                                            ctypes.POINTER(SO100ReplayStep), _P]
+    lib.so100_replay_stage_nstep.argtypes = [_P, ctypes.POINTER(SO100Replay), ctypes.POINTER(SO100ReplayNstep), _P, _P,
+                                             _P, _P]
+    lib.so100_replay_sample_nstep.argtypes = [_P, ctypes.POINTER(SO100Replay), ctypes.POINTER(SO100ReplayNstep),
+                                              ctypes.c_int, ctypes.c_uint64, ctypes.POINTER(SO100ReplayOut),
+                                              ctypes.POINTER(SO100ReplayNstepOut), _P]
     lib.so100_hull_cells.argtypes = [_P, _P, _P, ctypes.c_int]
     lib.so100_hull_blocks.argtypes = [_P, _P, ctypes.c_int]
     lib.so100_hull_support_probe.argtypes = [_P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P]
@@ -476,7 +517,8 @@ def load():
                "so100_her_step_bytes", "so100_her_out_bytes", "so100_her_limits", "so100_her_push",
                "so100_her_discard", "so100_her_scan", "so100_her_sample", "so100_replay_bytes",
                "so100_replay_step_bytes", "so100_replay_out_bytes", "so100_replay_push", "so100_replay_stage",
-               "so100_replay_scan", "so100_replay_sample"):
+               "so100_replay_scan", "so100_replay_sample", "so100_replay_nstep_bytes", "so100_replay_nstep_out_bytes",
+               "so100_replay_push_nstep", "so100_replay_stage_nstep", "so100_replay_sample_nstep"):
         getattr(lib, fn).restype = ctypes.c_int
     lib.so100_struct_sizes.argtypes = [_P, _P]
     lib.so100_struct_sizes.restype = ctypes.c_int
@@ -515,7 +557,9 @@ def load():
                                  f"{ctypes.sizeof(SO100NormRet)}")
     for fn, mirror in (("so100_her_bytes", SO100Her), ("so100_her_step_bytes", SO100HerStep),
                        ("so100_her_out_bytes", SO100HerOut), ("so100_replay_bytes", SO100Replay),
-                       ("so100_replay_step_bytes", SO100ReplayStep), ("so100_replay_out_bytes", SO100ReplayOut)):
+                       ("so100_replay_step_bytes", SO100ReplayStep), ("so100_replay_out_bytes", SO100ReplayOut),
+                       ("so100_replay_nstep_bytes", SO100ReplayNstep),
+                       ("so100_replay_nstep_out_bytes", SO100ReplayNstepOut)):
         if getattr(lib, fn)() != ctypes.sizeof(mirror):
             raise NativeLibraryError(f"struct layout mismatch: {fn} {getattr(lib, fn)()} vs {ctypes.sizeof(mirror)}")
     _lib = lib
@@ -554,7 +598,9 @@ EXPORTED_SYMBOLS = ("so100_abi_version", "so100_last_error", "so100_source_hash"
                     "so100_her_step_bytes", "so100_her_out_bytes", "so100_her_limits", "so100_her_storage_bytes",
                     "so100_her_push", "so100_her_discard", "so100_her_scan", "so100_her_sample", "so100_replay_bytes",
                     "so100_replay_step_bytes", "so100_replay_out_bytes", "so100_replay_storage_bytes",
-                    "so100_replay_push", "so100_replay_stage", "so100_replay_scan", "so100_replay_sample")
+                    "so100_replay_push", "so100_replay_stage", "so100_replay_scan", "so100_replay_sample",
+                    "so100_replay_nstep_bytes", "so100_replay_nstep_out_bytes", "so100_replay_nstep_storage_bytes",
+                    "so100_replay_push_nstep", "so100_replay_stage_nstep", "so100_replay_sample_nstep")
 
 
 def source_hash():

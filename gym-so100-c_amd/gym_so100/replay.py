@@ -5,8 +5,10 @@ option checks, which touch no device.
 
 Beside it the uniform replay buffer of the arm tasks: SB3 ``DictReplayBuffer``'s storage for state and
 pixel observations, with DrQ's random-shift augmentation in the sample launch (csrc/so100_replay.hip).
-``SO100VecEnv(uniform_replay=...)`` owns one ``UniformReplay`` (``env.uniform_replay``)."""
+``SO100VecEnv(uniform_replay=...)`` owns one ``UniformReplay`` (``env.uniform_replay``).  With the option ``n_step`` it
+also keeps the ``ends`` bytes and samples n-step returns."""
 import ctypes
+import math
 
 import numpy as np
 
@@ -197,6 +199,27 @@ class HerReplay:
 # (scripts/train_sac.py): a plain DictReplayBuffer
 UNIFORM_REPLAY_DEFAULTS = dict(buffer_size=None, augment=None, seed=None)
 AUGMENT_DEFAULT_PAD = 4          # DrQ's random shift: pad by 4, crop at a random offset
+# the n-step options, in a table of their own: n_step None = a buffer exactly as without them (no ``ends``, the plain
+# launches); an int (1 included) = the ``_nstep`` launches and the extra sample keys.  gamma: SB3's default
+UNIFORM_REPLAY_NSTEP_DEFAULTS = dict(n_step=None, gamma=0.99)
+
+
+def nstep_window(n_step, gamma, T=None):
+    """The checked (n_step, gamma) of an n-step window: n_step an int in 1..16 (and <= T - 1 when T is given), gamma a
+    finite float in [0, 1]; ValueError otherwise."""
+    if isinstance(n_step, (bool, np.bool_)) or not isinstance(n_step, (int, np.integer)):
+        raise ValueError(f"uniform_replay: n_step {n_step!r} must be an integer")
+    n_step = int(n_step)
+    if not 1 <= n_step <= _native.SO100_REPLAY_MAX_NSTEP:
+        raise ValueError(f"uniform_replay: n_step {n_step} outside 1..{_native.SO100_REPLAY_MAX_NSTEP}")
+    if T is not None and n_step > T - 1:
+        raise ValueError(f"uniform_replay: n_step {n_step} exceeds the {T - 1} transitions that {T} slots per env hold")
+    if isinstance(gamma, (bool, np.bool_)) or not isinstance(gamma, (int, float, np.integer, np.floating)):
+        raise ValueError(f"uniform_replay: gamma {gamma!r} must be a number")
+    gamma = float(gamma)
+    if not (math.isfinite(gamma) and 0.0 <= gamma <= 1.0):
+        raise ValueError(f"uniform_replay: gamma {gamma} must be finite and in [0, 1]")
+    return n_step, gamma
 
 
 def augment_pad(augment):
@@ -224,16 +247,25 @@ def uniform_replay_options(uniform_replay, num_envs=None, task="so100_cube_to_bi
     -> the defaults overridden by it, with ``pad`` (the augmentation's) and, when ``num_envs`` is given, ``T =
     buffer_size // num_envs`` (the slots per env) added.  Raises ValueError for unknown keys and bad values, and, given
     the env's arguments, for the GoalEnv (``replay=`` is its buffer), without auto-reset, for fewer than 2 slots per env
-    and for an augmentation without pixel observations."""
+    and for an augmentation without pixel observations.  The keys ``n_step`` (1..16, at most T - 1) and ``gamma`` (finite,
+    in [0, 1], default 0.99; a ValueError without ``n_step``) turn the n-step returns on: the result's ``n_step`` is None
+    without them."""
     if uniform_replay is None:
         return None
     if not isinstance(uniform_replay, dict):
         raise ValueError("uniform_replay: None or a dict(" + ", ".join(f"{k}=" for k in UNIFORM_REPLAY_DEFAULTS) + ")")
-    unknown = set(uniform_replay) - set(UNIFORM_REPLAY_DEFAULTS)
+    known = {**UNIFORM_REPLAY_DEFAULTS, **UNIFORM_REPLAY_NSTEP_DEFAULTS}
+    unknown = set(uniform_replay) - set(known)
     if unknown:
-        raise ValueError(f"uniform_replay: unknown keys {sorted(unknown)}; known: {sorted(UNIFORM_REPLAY_DEFAULTS)}")
+        raise ValueError(f"uniform_replay: unknown keys {sorted(unknown)}; known: {sorted(known)}")
     o = dict(UNIFORM_REPLAY_DEFAULTS)
+    o["n_step"] = None
     o.update(uniform_replay)
+    if o["n_step"] is None:
+        if "gamma" in o:
+            raise ValueError("uniform_replay: gamma is the n-step window's; it needs n_step=")
+    else:
+        o["n_step"], o["gamma"] = nstep_window(o["n_step"], o.get("gamma", UNIFORM_REPLAY_NSTEP_DEFAULTS["gamma"]))
     if o["buffer_size"] is None:
         raise ValueError("uniform_replay: buffer_size (slots over all envs) is required")
     if isinstance(o["buffer_size"], (bool, np.bool_)) or not isinstance(o["buffer_size"], (int, np.integer)):
@@ -260,6 +292,8 @@ def uniform_replay_options(uniform_replay, num_envs=None, task="so100_cube_to_bi
             raise ValueError(f"uniform_replay: {T} slots x {num_envs} envs >= 2^31")
         if o["pad"] > 0 and obs_type != "so100_pixels_agent_pos":
             raise ValueError("uniform_replay: augment shifts images; it needs obs_type='so100_pixels_agent_pos'")
+        if o["n_step"] is not None:
+            nstep_window(o["n_step"], o["gamma"], T)
         o["T"] = T
     return o
 
@@ -301,6 +335,14 @@ class UniformReplay:
         want = self.lib.so100_replay_storage_bytes(n, T, A, P)
         if held != want:
             raise RuntimeError(f"uniform_replay: the arrays hold {held} bytes, so100_replay_storage_bytes {want}")
+        self.n_step, self.gamma = self.o.get("n_step"), self.o.get("gamma")
+        self._nstep = None          # the n-step record: None = the plain launches, no `ends`
+        if self.n_step is not None:
+            self.ends = z(T, n, dtype=u8)
+            if self.ends.numel() != self.lib.so100_replay_nstep_storage_bytes(n, T):
+                raise RuntimeError(f"uniform_replay: ends holds {self.ends.numel()} bytes, "
+                                   f"so100_replay_nstep_storage_bytes {self.lib.so100_replay_nstep_storage_bytes(n, T)}")
+            self._nstep = _native.SO100ReplayNstep(n_step=self.n_step, gamma=self.gamma, ends=_native.ptr(self.ends))
         self.cursor, self.count = self.store["meta"]
         self._total = self.store["prefix"][n:]
         self._rec = _native.SO100Replay(n=n, T=T, action_dim=A, planes=layout[0], H=layout[1], W=layout[2],
@@ -314,6 +356,12 @@ class UniformReplay:
         """the reset envs (mask: the env's uint8 mask or None = all): their fresh observation and image are staged at
         their cursors"""
         env = self.env
+        if self._nstep is not None:
+            _native.check(self.lib.so100_replay_stage_nstep(env._handle, ctypes.byref(self._rec),
+                                                            ctypes.byref(self._nstep), _native.ptr(mask),
+                                                            _native.ptr(env.obs), _native.ptr(env.pixels),
+                                                            env._stream()), "so100_replay_stage_nstep")
+            return
         _native.check(self.lib.so100_replay_stage(env._handle, ctypes.byref(self._rec), _native.ptr(mask),
                                                   _native.ptr(env.obs), _native.ptr(env.pixels), env._stream()),
                       "so100_replay_stage")
@@ -324,8 +372,13 @@ class UniformReplay:
         step = _native.SO100ReplayStep(obs=P(env.obs), final_obs=P(env.final_obs), action=P(command),
                                        reward=P(env.reward), terminated=P(env.terminated), truncated=P(env.truncated),
                                        diverged=P(env.diverged), pixels=P(env.pixels), final_pixels=P(env.final_pixels))
-        _native.check(self.lib.so100_replay_push(env._handle, ctypes.byref(self._rec), ctypes.byref(step),
-                                                 env._stream()), "so100_replay_push")
+        if self._nstep is not None:
+            _native.check(self.lib.so100_replay_push_nstep(env._handle, ctypes.byref(self._rec),
+                                                           ctypes.byref(self._nstep), ctypes.byref(step),
+                                                           env._stream()), "so100_replay_push_nstep")
+        else:
+            _native.check(self.lib.so100_replay_push(env._handle, ctypes.byref(self._rec), ctypes.byref(step),
+                                                     env._stream()), "so100_replay_push")
         self._dirty = True
 
     # ------------------------------------------------------------------ the user's side
@@ -345,7 +398,7 @@ class UniformReplay:
         """``valid_count`` on the host (waits for the device)"""
         return int(self.valid_count.item())
 
-    def sample(self, batch_size, augment=None, normalize=False, check=False):
+    def sample(self, batch_size, augment=None, normalize=False, check=False, n_step=None, gamma=None):
         """A batch of ``batch_size`` transitions as a dict of device tensors.  Pixel env: ``pixels`` / ``next_pixels``
         ([B, *env.pixels.shape[1:]] uint8), ``agent_pos`` / ``next_agent_pos`` (columns 9:15 of the state rows) and
         ``state`` / ``next_state`` (the 15-float rows); state env: ``obs`` / ``next_obs``.  Both: ``actions``,
@@ -354,12 +407,23 @@ class UniformReplay:
         augment: None -> the buffer's option; False -> the stored images; True, an int or dict(pad=) as in the options.
         normalize: ``agent_pos`` (or ``obs``) and its ``next_`` twin through ``env.normalize_obs`` (ValueError without a
         normaliser); images and rewards are never touched.  check: read ``valid_count`` and raise ValueError when it is
-        0 (an empty buffer otherwise gives rows of zeros with slot -1)."""
+        0 (an empty buffer otherwise gives rows of zeros with slot -1).
+        A buffer built with ``n_step`` also returns ``discounts`` (gamma^m, the factor of the bootstrap value),
+        ``n_steps`` (m, the transitions of the row's window) and ``last_slot``; ``rewards`` is then the discounted sum
+        over the window, and ``dones`` and the ``next_`` entries are those of its last transition.  n_step, gamma:
+        another window for this call (the ``ends`` bytes are stored regardless); ValueError on a buffer built without
+        ``n_step``."""
         import torch
         B = _int("batch_size", batch_size)
         if B < 0:
             raise ValueError(f"uniform_replay: batch_size {B} must be >= 0")
         env = self.env
+        if self._nstep is None:
+            if n_step is not None or gamma is not None:
+                raise ValueError("uniform_replay: sample(n_step=, gamma=) needs a buffer built with n_step=")
+        else:
+            window = nstep_window(self.n_step if n_step is None else n_step, self.gamma if gamma is None else gamma,
+                                  self.T)
         pad = self.pad if augment is None else augment_pad(augment)
         if pad > 0 and not self.P:
             raise ValueError("uniform_replay: augment shifts images; it needs obs_type='so100_pixels_agent_pos'")
@@ -376,7 +440,18 @@ class UniformReplay:
             raw["pixels"] = e(B, *self.image_shape, dtype=torch.uint8)
             raw["next_pixels"] = e(B, *self.image_shape, dtype=torch.uint8)
         rec = _native.SO100ReplayOut(**{k: _native.ptr(t) for k, t in raw.items()})
-        if B:                        # (an empty tensor has no address to hand over)
+        if self._nstep is not None:
+            more = {"discounts": e(B), "nsteps": e(B, dtype=i32), "last_slot": e(B, dtype=i32)}
+            if B:
+                self._rec.pad = pad
+                ns = _native.SO100ReplayNstep(n_step=window[0], gamma=window[1], ends=_native.ptr(self.ends))
+                nrec = _native.SO100ReplayNstepOut(**{k: _native.ptr(t) for k, t in more.items()})
+                _native.check(self.lib.so100_replay_sample_nstep(env._handle, ctypes.byref(self._rec), ctypes.byref(ns),
+                                                                 B, ctypes.c_uint64(self.calls), ctypes.byref(rec),
+                                                                 ctypes.byref(nrec), env._stream()),
+                              "so100_replay_sample_nstep")
+            raw["discounts"], raw["n_steps"], raw["last_slot"] = more["discounts"], more["nsteps"], more["last_slot"]
+        elif B:                      # (an empty tensor has no address to hand over)
             self._rec.pad = pad
             _native.check(self.lib.so100_replay_sample(env._handle, ctypes.byref(self._rec), B,
                                                        ctypes.c_uint64(self.calls), ctypes.byref(rec), env._stream()),

@@ -470,6 +470,9 @@ class SO100HerReplayBuffer(_ReplayBufferBase):
 # SB3's ReplayBufferSamples / DictReplayBufferSamples, field for field (type_aliases.py); the values are device tensors
 ReplaySamples = collections.namedtuple("ReplaySamples",
                                        ["observations", "actions", "next_observations", "dones", "rewards"])
+# the same five and the factor of the bootstrap value, gamma^m, for a buffer built with n_step: what a learner with
+# n-step targets reads from its samples
+NStepReplaySamples = collections.namedtuple("NStepReplaySamples", ReplaySamples._fields + ("discounts",))
 
 
 class SO100ReplayBuffer(_ReplayBufferBase):
@@ -478,15 +481,24 @@ class SO100ReplayBuffer(_ReplayBufferBase):
     replay_buffer_class=SO100ReplayBuffer, replay_buffer_kwargs=dict(env=env))``.  The env has stored every transition by
     the time the learner calls ``add``, so ``add`` does nothing; ``sample`` draws (and, with ``augment``, shifts the
     images) on the device and returns torch tensors there.  SB3's own storage is never allocated (its ``__init__`` is
-    not run)."""
+    not run).  ``n_steps`` and ``gamma``, which a learner with n-step targets passes to its buffer, are ignored for an
+    env built without ``uniform_replay=dict(n_step=...)``; with it they must agree with the env's options (ValueError
+    otherwise), and ``sample`` returns ``NStepReplaySamples``: the five fields and ``discounts`` [B, 1]."""
 
     def __init__(self, buffer_size=None, observation_space=None, action_space=None, env=None, device="auto", n_envs=None,
-                 **_ignored):
+                 n_steps=None, gamma=None, **_ignored):
         venv = getattr(env, "venv", env)
         if venv is None or getattr(venv, "uniform_replay", None) is None:
             raise ValueError("SO100ReplayBuffer needs env=: an SO100SB3VecEnv / SO100VecEnv built with "
                              "uniform_replay=...")
         self.venv, self.replay = venv, venv.uniform_replay
+        if self.replay.n_step is not None:
+            if n_steps is not None and int(n_steps) != self.replay.n_step:
+                raise ValueError(f"SO100ReplayBuffer: n_steps {n_steps} but the env was built with uniform_replay="
+                                 f"dict(n_step={self.replay.n_step})")
+            if gamma is not None and float(gamma) != self.replay.gamma:
+                raise ValueError(f"SO100ReplayBuffer: gamma {gamma} but the env was built with uniform_replay="
+                                 f"dict(gamma={self.replay.gamma})")
         self.buffer_size = self.replay.T                     # SB3 counts slots per env
         self.n_envs = venv.num_envs
         self.observation_space = observation_space if observation_space is not None else \
@@ -513,5 +525,9 @@ class SO100ReplayBuffer(_ReplayBufferBase):
             nxt = {"pixels": b["next_pixels"], "agent_pos": b["next_agent_pos"]}
         else:
             obs, nxt = b["obs"], b["next_obs"]
+        if "discounts" in b:
+            return NStepReplaySamples(observations=obs, actions=b["actions"], next_observations=nxt,
+                                      dones=b["dones"].reshape(-1, 1), rewards=b["rewards"].reshape(-1, 1),
+                                      discounts=b["discounts"].reshape(-1, 1))
         return ReplaySamples(observations=obs, actions=b["actions"], next_observations=nxt,
                              dones=b["dones"].reshape(-1, 1), rewards=b["rewards"].reshape(-1, 1))

@@ -293,7 +293,11 @@ class SO100VecEnv:
             an int pad, dict(pad=)): DrQ's random shift of the two sampled images, in the sample launch.  Depth and
             segmentation images are not stored.  ``step_async_raw`` stores nothing.  ValueError for unknown keys and bad
             values, for task="so100_goal" (``replay=`` is its buffer), autoreset=False, buffer_size // num_envs < 2 and
-            ``augment`` without pixel observations.
+            ``augment`` without pixel observations.  ``n_step`` (1..16, at most the slots per env - 1) with ``gamma``
+            (default 0.99) turns on n-step returns: push and reset then also record where episodes
+            end (a done, a ``reset(mask)`` in mid-episode, a dropped step), and ``sample`` sums the discounted rewards
+            over a window that stays within one episode and gains the keys ``discounts``, ``n_steps`` and
+            ``last_slot``.  Without the key nothing changes.
     """
 
     def __init__(self, num_envs, task="so100_cube_to_bin", obs_type="so100_state", device="cuda:0", seed=0,

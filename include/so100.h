@@ -820,6 +820,80 @@ int so100_replay_scan(so100_env* env, const so100_replay* replay, void* stream);
 int so100_replay_sample(so100_env* env, const so100_replay* replay, int batch, uint64_t call, const so100_replay_out* out,
                         void* stream);
 
+/* ---- (additions to ABI 25) n-step returns in the uniform replay buffer: the multi-step target of
+ * DrQ-v2 (n = 3) and of SB3's off-policy `n_steps=`, gathered and summed by the sample launch.  Only the push and the
+ * stage see where an episode ends (a truncation, a reset(mask) in mid-episode and a dropped step leave no trace in
+ * so100_replay), so they record it: one more caller-owned array, `ends`, uint8 [T][n], slot-major, zero at the start,
+ * named by so100_replay_nstep beside so100_replay.  ends[s][e] != 0: the transition in slot s of env e is the last one
+ * that an n-step window may include from its episode.  Extra storage: T n bytes (so100_replay_nstep_storage_bytes).
+ * Below n stays the number of envs; n_step, gamma and ends are the fields of so100_replay_nstep.
+ *
+ * so100_replay_push_nstep (one launch: so100_replay_push's kernel compiled with the extra pointer): rules 1-5 of
+ *   so100_replay_push, and in the same workgroup, with c = cursor[e] and k = count[e] as read before the push:
+ *   6. ends[c] <- (terminated[e] | truncated[e]) != 0, as 0 / 1.
+ *   7. diverged[e] non-zero and k > 0: ends[(c - 1) mod T] <- 1: the episode was cut, its last stored transition closes
+ *      it; the slot c is used again by the next episode.
+ * so100_replay_stage_nstep (one launch): what so100_replay_stage does, and for every staged env with count[e] > 0:
+ *   ends[(cursor[e] - 1) mod T] <- 1: a reset in mid-episode cuts the episode there (after a finished episode the byte
+ *   is 1 already).
+ * so100_replay_sample_nstep, batch element i (one launch: so100_replay_sample's kernel with the window compiled in; it
+ *   reads prefix, so a scan must follow the last push):
+ *   1. The pick is so100_replay_sample's: (e, slot s) from draw(0); kidx = r - prefix[e-1] is the index of s among env
+ *      e's valid transitions, oldest = 0.  So for the same (seed, call, i) the outputs obs, actions, env, slot, shift
+ *      and pixels are bit-equal to so100_replay_sample's, for every n_step.
+ *   2. m = the smallest j in 1..n_step with j == n_step, or ends[(s + j - 1) mod T][e] != 0, or kidx + j == count[e]
+ *      (the window has reached the newest stored transition; it never waits for a later push).
+ *   3. In float32, each product rounded, then each sum (no fused multiply-add): R = reward[s][e], g = gamma; for
+ *      j = 1..m-1: R = R + g * reward[(s + j) mod T][e], then g = g * gamma.  rewards[i] = R, discounts[i] = g (gamma
+ *      for m = 1: the factor of the bootstrap value), nsteps[i] = m, last_slot[i] = (s + m - 1) mod T.
+ *   4. next_obs, dones (the stored terminated) and next_pixels come from last_slot; ends is a superset of the terminated
+ *      flags, so a terminal transition always closes its window.  The next image takes the shift of draw(3), as in
+ *      so100_replay_sample.
+ *   5. total == 0: the rows of so100_replay_sample's empty buffer, and nsteps[i] = 0, discounts[i] = 0,
+ *      last_slot[i] = -1.
+ *   6. n_step == 1 gives so100_replay_sample's outputs bit for bit (and discounts = gamma, nsteps = 1, last_slot = slot).
+ *   Every index read from meta or prefix is clamped into its range before it addresses memory, and every window slot is
+ *   taken mod T; the bytes of ends only stop a window.
+ * The window costs one more round of loads, not n_step: lane j of a batch element's 16 lanes (of a wave, in the image
+ * workgroups) reads ends and reward of slot s + j, whose addresses follow from s alone; a ballot gives m.  Hence
+ * SO100_REPLAY_MAX_NSTEP = 16. */
+#define SO100_REPLAY_MAX_NSTEP 16
+typedef struct so100_replay_nstep {
+  uint32_t size;            /* sizeof(so100_replay_nstep) */
+  int32_t  n_step;          /* 1..min(SO100_REPLAY_MAX_NSTEP, T - 1) */
+  float    gamma;           /* finite, in [0, 1] */
+  uint32_t reserved0;
+  uint8_t* ends;            /* [T][n] */
+} so100_replay_nstep;
+int so100_replay_nstep_bytes(void);
+/* The additional outputs of one so100_replay_sample_nstep call: device arrays of `batch` rows. */
+typedef struct so100_replay_nstep_out {
+  uint32_t size;            /* sizeof(so100_replay_nstep_out) */
+  uint32_t reserved0;
+  float*   discounts;       /* [B]: gamma^m */
+  int32_t* nsteps;          /* [B]: m */
+  int32_t* last_slot;       /* [B] */
+} so100_replay_nstep_out;
+int so100_replay_nstep_out_bytes(void);
+/* Bytes of `ends`: T n, in 64-bit arithmetic; -1 (text in so100_last_error) for n < 0, T < 2 or T * n >= 2^31.
+ * so100_replay_storage_bytes does not count them. */
+int64_t so100_replay_nstep_storage_bytes(int n, int T);
+/* All three: as their namesakes above (one launch on `stream`, no allocation, no synchronisation, no atomics; nothing
+ * launched for n = 0 or batch = 0), with the same refusals in the same order under their own names.  The refusals of
+ * the n-step records sit in that order as follows.  After the numbers of so100_replay and the call's own records (batch,
+ * out, step and their sizes) and before the NULL env: NULL nstep, a wrong `size` of it, an n_step outside
+ * 1..min(SO100_REPLAY_MAX_NSTEP, T - 1), a gamma that is not finite or outside [0, 1] (all three calls check both
+ * numbers), (sample) NULL nout or a wrong `size` of it.  After the arrays of so100_replay and before the pointers of step
+ * or out: NULL ends.  Last: a NULL pointer of nout. */
+int so100_replay_push_nstep(so100_env* env, const so100_replay* replay, const so100_replay_nstep* nstep,
+                            const so100_replay_step* step, void* stream);
+int so100_replay_stage_nstep(so100_env* env, const so100_replay* replay, const so100_replay_nstep* nstep,
+                             const uint8_t* mask /* [n] or NULL */, const float* obs /* [n][15] */,
+                             const uint8_t* pixels /* [n][P], NULL with P == 0 */, void* stream);
+int so100_replay_sample_nstep(so100_env* env, const so100_replay* replay, const so100_replay_nstep* nstep, int batch,
+                              uint64_t call, const so100_replay_out* out, const so100_replay_nstep_out* nout,
+                              void* stream);
+
 /* Batched sparse GoalEnv reward (env.py:341-353): out[i] = ||a_i - d_i|| < threshold ? 0 : -1. */
 int so100_goal_reward(so100_env* env, int n, const float* achieved, const float* desired, float* out,
                       void* stream);
