@@ -86,6 +86,14 @@ hipError_t launch_replay_stage_nstep(const so100_replay&, const so100_replay_nst
                                      const uint8_t*, hipStream_t);
 hipError_t launch_replay_sample_nstep(const so100_replay&, const so100_replay_out&, const so100_replay_nstep&,
                                       const so100_replay_nstep_out&, int, uint64_t, hipStream_t);
+hipError_t launch_replay_push_per(const so100_replay&, const so100_replay_per&, const so100_replay_nstep*,
+                                  const so100_replay_step&, hipStream_t);
+hipError_t launch_replay_per_scan(const so100_replay&, const so100_replay_per&, hipStream_t);
+hipError_t launch_replay_sample_per(const so100_replay&, const so100_replay_out&, const so100_replay_per&,
+                                    const so100_replay_per_out&, const so100_replay_nstep*,
+                                    const so100_replay_nstep_out*, int, uint64_t, hipStream_t);
+hipError_t launch_replay_per_update(const so100_replay&, const so100_replay_per&, int, const int32_t*, const int32_t*,
+                                    const float*, hipStream_t);
 }  // namespace so100
 
 using so100::DevModel;
@@ -1932,6 +1940,105 @@ static int so100_replay_sample_impl(so100_env* env, const so100_replay* h, const
   return e == hipSuccess ? 0 : fail_hip(fn, e);
 }
 
+// the prioritised calls (include/so100.h, the numbered refusals above so100_replay_push_per).  replay_check_per: 2-5;
+// replay_check_per_ptrs: the arrays of 9 up to max_prio
+static int replay_check_per(const char* fn, const so100_replay* h, const so100_replay_per* pr,
+                            const so100_replay_nstep* ns) {
+  if (!pr) return her_fail(fn, "NULL per");
+  if (pr->size != sizeof(so100_replay_per)) return size_mismatch(fn, "so100_replay_per", pr->size, sizeof(so100_replay_per));
+  if (!(pr->alpha >= 0.f && pr->alpha <= 1.f)) return her_fail(fn, "alpha outside [0, 1]");      // false for NaN
+  if (!(pr->beta >= 0.f && pr->beta <= 1.f)) return her_fail(fn, "beta outside [0, 1]");
+  if (!(pr->eps > 0.f && std::isfinite(pr->eps))) return her_fail(fn, "eps not finite or <= 0");
+  if (ns)
+    if (int rc = replay_check_nstep(fn, h, ns)) return rc;
+  return 0;
+}
+static int replay_check_per_ptrs(const char* fn, const so100_env* env, const so100_replay* h, const so100_replay_per* pr,
+                                 const so100_replay_nstep* ns) {
+  if (int rc = replay_check_ptrs(fn, env, h)) return rc;
+  if (ns)
+    if (int rc = replay_check_ends(fn, ns)) return rc;
+  if (!pr->prio || !pr->sum || !pr->max_prio) return her_fail(fn, "NULL array in so100_replay_per");
+  return 0;
+}
+
+static int so100_replay_push_per_impl(so100_env* env, const so100_replay* h, const so100_replay_per* pr,
+                                      const so100_replay_nstep* ns, const so100_replay_step* st, void* stream) {
+  const char* fn = "so100_replay_push_per";
+  if (int rc = replay_check(fn, h)) return rc;
+  if (int rc = replay_check_per(fn, h, pr, ns)) return rc;
+  if (!st) return her_fail(fn, "NULL step");
+  if (st->size != sizeof(so100_replay_step))
+    return size_mismatch(fn, "so100_replay_step", st->size, sizeof(so100_replay_step));
+  if (int rc = replay_check_per_ptrs(fn, env, h, pr, ns)) return rc;
+  if (!st->obs || !st->final_obs || !st->action || !st->reward || !st->terminated || !st->truncated)
+    return her_fail(fn, "NULL pointer in so100_replay_step");
+  if (h->P == 0 && (st->pixels || st->final_pixels)) return her_fail(fn, "image pointers in so100_replay_step with P == 0");
+  if (h->P > 0 && (!st->pixels || !st->final_pixels))
+    return her_fail(fn, "NULL image pointer in so100_replay_step with P > 0");
+  if (h->n == 0) return 0;
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_replay_push_per(*h, *pr, ns, *st, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip(fn, e);
+}
+
+static int so100_replay_per_scan_impl(so100_env* env, const so100_replay* h, const so100_replay_per* pr, void* stream) {
+  const char* fn = "so100_replay_per_scan";
+  if (int rc = replay_check(fn, h)) return rc;
+  if (int rc = replay_check_per(fn, h, pr, nullptr)) return rc;
+  if (int rc = replay_check_per_ptrs(fn, env, h, pr, nullptr)) return rc;
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_replay_per_scan(*h, *pr, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip(fn, e);
+}
+
+static int so100_replay_sample_per_impl(so100_env* env, const so100_replay* h, const so100_replay_per* pr,
+                                        const so100_replay_nstep* ns, int batch, uint64_t call,
+                                        const so100_replay_out* o, const so100_replay_nstep_out* no,
+                                        const so100_replay_per_out* po, void* stream) {
+  const char* fn = "so100_replay_sample_per";
+  if (int rc = replay_check(fn, h)) return rc;
+  if (int rc = replay_check_per(fn, h, pr, ns)) return rc;
+  if (no && !ns) return her_fail(fn, "nout without nstep");
+  if (ns && !no) return her_fail(fn, "NULL nout with nstep");
+  if (no && no->size != sizeof(so100_replay_nstep_out))
+    return size_mismatch(fn, "so100_replay_nstep_out", no->size, sizeof(so100_replay_nstep_out));
+  if (!po) return her_fail(fn, "NULL pout");
+  if (po->size != sizeof(so100_replay_per_out))
+    return size_mismatch(fn, "so100_replay_per_out", po->size, sizeof(so100_replay_per_out));
+  if (!o) return her_fail(fn, "NULL out");
+  if (o->size != sizeof(so100_replay_out)) return size_mismatch(fn, "so100_replay_out", o->size, sizeof(so100_replay_out));
+  if (batch < 0) return her_fail(fn, "batch < 0");
+  if (int rc = replay_check_per_ptrs(fn, env, h, pr, ns)) return rc;
+  if (!o->obs || !o->next_obs || !o->actions || !o->rewards || !o->dones || !o->env || !o->slot || !o->shift)
+    return her_fail(fn, "NULL pointer in so100_replay_out");
+  if (h->P == 0 && (o->pixels || o->next_pixels)) return her_fail(fn, "image pointers in so100_replay_out with P == 0");
+  if (h->P > 0 && (!o->pixels || !o->next_pixels))
+    return her_fail(fn, "NULL image pointer in so100_replay_out with P > 0");
+  if (ns && (!no->discounts || !no->nsteps || !no->last_slot))
+    return her_fail(fn, "NULL pointer in so100_replay_nstep_out");
+  if (!po->probs || !po->weights) return her_fail(fn, "NULL pointer in so100_replay_per_out");
+  if (batch == 0) return 0;
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_replay_sample_per(*h, *o, *pr, *po, ns, no, batch, call, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip(fn, e);
+}
+
+static int so100_replay_per_update_impl(so100_env* env, const so100_replay* h, const so100_replay_per* pr, int batch,
+                                        const int32_t* env_idx, const int32_t* slot_idx, const float* td_abs,
+                                        void* stream) {
+  const char* fn = "so100_replay_per_update";
+  if (int rc = replay_check(fn, h)) return rc;
+  if (int rc = replay_check_per(fn, h, pr, nullptr)) return rc;
+  if (batch < 0) return her_fail(fn, "batch < 0");
+  if (int rc = replay_check_per_ptrs(fn, env, h, pr, nullptr)) return rc;
+  if (!env_idx || !slot_idx || !td_abs) return her_fail(fn, "NULL env_idx, slot_idx or td_abs");
+  if (batch == 0 || h->n == 0) return 0;
+  DeviceGuard g(env->device);
+  hipError_t e = so100::launch_replay_per_update(*h, *pr, batch, env_idx, slot_idx, td_abs, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail_hip(fn, e);
+}
+
 static int so100_norm_return_impl(so100_env* env, const so100_norm_ret* a, int n, const float* reward,
                                   const uint8_t* terminated, const uint8_t* truncated, double* ret, double* stats,
                                   void* work, float* reward_norm, void* stream) {
@@ -2133,6 +2240,53 @@ int so100_replay_stage_nstep(so100_env* env, const so100_replay* replay, const s
     return so100_replay_stage_impl(env, replay, nstep, true, mask, obs, pixels, stream);
   } catch (...) {
     return caught("so100_replay_stage_nstep");
+  }
+}
+
+int so100_replay_per_bytes(void) { return (int)sizeof(so100_replay_per); }
+int so100_replay_per_out_bytes(void) { return (int)sizeof(so100_replay_per_out); }
+
+int64_t so100_replay_per_storage_bytes(int n, int T) {
+  if (n < 0 || T < 2 || (long long)T * n >= (1ll << 31)) {
+    fail("so100_replay_per_storage_bytes: n < 0, T < 2 or T * n >= 2^31");
+    return -1;
+  }
+  return 4ll * T * n + 8ll * ((long long)n + 1) + 8;
+}
+
+int so100_replay_push_per(so100_env* env, const so100_replay* replay, const so100_replay_per* per,
+                          const so100_replay_nstep* nstep, const so100_replay_step* step, void* stream) {
+  try {
+    return so100_replay_push_per_impl(env, replay, per, nstep, step, stream);
+  } catch (...) {
+    return caught("so100_replay_push_per");
+  }
+}
+
+int so100_replay_per_scan(so100_env* env, const so100_replay* replay, const so100_replay_per* per, void* stream) {
+  try {
+    return so100_replay_per_scan_impl(env, replay, per, stream);
+  } catch (...) {
+    return caught("so100_replay_per_scan");
+  }
+}
+
+int so100_replay_sample_per(so100_env* env, const so100_replay* replay, const so100_replay_per* per,
+                            const so100_replay_nstep* nstep, int batch, uint64_t call, const so100_replay_out* out,
+                            const so100_replay_nstep_out* nout, const so100_replay_per_out* pout, void* stream) {
+  try {
+    return so100_replay_sample_per_impl(env, replay, per, nstep, batch, call, out, nout, pout, stream);
+  } catch (...) {
+    return caught("so100_replay_sample_per");
+  }
+}
+
+int so100_replay_per_update(so100_env* env, const so100_replay* replay, const so100_replay_per* per, int batch,
+                            const int32_t* env_idx, const int32_t* slot_idx, const float* td_abs, void* stream) {
+  try {
+    return so100_replay_per_update_impl(env, replay, per, batch, env_idx, slot_idx, td_abs, stream);
+  } catch (...) {
+    return caught("so100_replay_per_update");
   }
 }
 

@@ -34,6 +34,13 @@
 // same three kernel bodies, instantiated a second time with the `ends` bytes: push and stage mark where an episode ends,
 // the sample reads the window's n_step `ends` bytes and rewards in one round (one slot per lane), finds its length by a
 // ballot and sums the rewards in a fixed order by shuffles.  The plain entry points launch the instantiations without.
+//
+// Prioritised replay (so100_replay_push_per, so100_replay_per_scan, so100_replay_sample_per, so100_replay_per_update;
+// DESIGN.md §3.14).  The push and sample bodies instantiated once more per combination with the uint32 fixed-point
+// priorities; the plain and n-step entry points launch the instantiations without, as before.  The sums are uint64, so a
+// scan in any order gives the same bits: per-env sums by the whole device, then one workgroup's scan over the envs (the
+// only LDS of this file, and still no wait for another workgroup).  The update holds the library's only atomics, an
+// integer maximum per applied row and one per wave: commutative, so the result is still a function of the inputs alone.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "so100.h"
@@ -112,19 +119,22 @@ struct RepPick {
   bool any;
 };
 
-// the first env e of [0, n) with prefix[e] > r (n - 1 when there is none), by bisection: any set of lanes
-__device__ __forceinline__ int find_env_bisect(const int32_t* prefix, int n, long long r) {
+// the first env e of [0, n) with prefix[e] > r (n - 1 when there is none), by bisection: any set of lanes.  (V, R): the
+// counts' (int32_t, long long) or the priority sums' (uint64_t, uint64_t)
+template <class V, class R>
+__device__ __forceinline__ int find_env_bisect(const V* prefix, int n, R r) {
   int lo = 0, hi = n - 1;
   for (int it = 0; it < 32 && lo < hi; it++) {
     const int mid = (int)(((long long)lo + hi) >> 1);
-    if ((long long)prefix[mid] > r) hi = mid; else lo = mid + 1;
+    if ((R)prefix[mid] > r) hi = mid; else lo = mid + 1;
   }
   return lo;
 }
 
 // the same env found by a whole wave (all 64 lanes active, r equal in all): each round the lanes probe 64 evenly spaced
 // candidates and a ballot narrows the range 64-fold, so 8,192 envs take 3 dependent loads where bisection takes 13
-__device__ __forceinline__ int find_env_wave(const int32_t* prefix, int n, long long r) {
+template <class V, class R>
+__device__ __forceinline__ int find_env_wave(const V* prefix, int n, R r) {
   const int lane = (int)threadIdx.x & 63;
   int lo = 0, cnt = n;                                   // the candidates are [lo, lo + cnt)
   for (int it = 0; it < 6 && cnt > 1; it++) {
@@ -132,7 +142,7 @@ __device__ __forceinline__ int find_env_wave(const int32_t* prefix, int n, long 
     const int last = lo + cnt - 1;
     const long long want = (long long)lo + (long long)(lane + 1) * step - 1;
     const int probe = want < last ? (int)want : last;    // nondecreasing in the lane, within [lo, last]
-    const bool below = (long long)prefix[probe] <= r;
+    const bool below = (R)prefix[probe] <= r;
     const int f = __popcll(__ballot(below));             // the lanes whose probe is still <= r: the first f
     if (f == 64) return last;                            // (no env of the range exceeds r)
     const long long nlo = (long long)lo + (long long)f * step;       // one past lane f - 1's probe
@@ -167,6 +177,69 @@ __device__ __forceinline__ RepPick replay_pick(const so100_replay& h, uint64_t c
   p.k = k;
   p.cnt = cnt;
   p.any = true;
+  return p;
+}
+
+// the prioritised pick of batch element i (so100_replay_sample_per, rules 1-4): r uniform in [0, total) of the priority
+// sums, the env by the same searches on 64-bit values, then the first of the env's valid slots, oldest first, whose
+// running sum exceeds rr.  The slots' addresses follow from the metadata alone, so the L lanes of the caller (WAVE: a
+// whole wave, one i per wave; else the 16 lanes [base, base + 16) of a batch element, all active, same i) split the cnt
+// slots into L runs of `per` consecutive ones and load them side by side, `per` independent loads per lane: one more
+// round trip on the chain, not cnt.  A shuffle prefix over the runs' sums and a ballot find the run; with per > 1 every
+// lane then walks that run again (the same addresses in all lanes, just loaded: L1 hits) without a branch on what it
+// reads.  q: the pick's priority, total: the sum the draw was scaled by.
+template <bool WAVE>
+__device__ __forceinline__ RepPick replay_pick_per(const so100_replay& h, const so100_replay_per& pr, uint64_t call,
+                                                   size_t i, uint32_t& q, uint64_t& total) {
+  constexpr int L = WAVE ? 64 : kRepLanes;
+  RepPick p = {0, -1, 0, 0, false};
+  q = 0u;
+  const int n = h.n, T = h.T;
+  total = pr.sum[n];
+  if (total == 0) return p;
+  const uint64_t r = __umul64hi(her_draw(h.seed, call, i, 0u), total);
+  const int e = WAVE ? find_env_wave<uint64_t, uint64_t>(pr.sum, n, r) : find_env_bisect<uint64_t, uint64_t>(pr.sum, n, r);
+  const uint64_t before_env = e > 0 ? pr.sum[e - 1] : 0ull;
+  const uint64_t rr = r >= before_env ? r - before_env : 0ull;
+  const int cur = clampi(h.meta[e], 0, T - 1);
+  const int cnt = clampi(h.meta[(size_t)n + e], 0, T - 1);
+  const int start = sub_mod(cur, cnt, T);
+  const int lane = (int)threadIdx.x & (L - 1), base = WAVE ? 0 : ((int)threadIdx.x & 48);
+  const int per = (cnt + L - 1) / L;                     // slots per lane: 1 up to L valid slots
+  uint64_t mine = 0;
+  for (int t = 0; t < per; t++) {
+    const int k = lane * per + t;                        // < L per < cnt + L <= T + 63
+    if (k < cnt) mine += pr.prio[(size_t)add_mod(start, k, T) * n + e];
+  }
+  uint64_t incl = mine;                                  // inclusive scan of the L runs' sums
+#pragma unroll
+  for (int off = 1; off < L; off <<= 1) {
+    const uint64_t up = __shfl_up(incl, off, L);
+    if (lane >= off) incl += up;
+  }
+  const unsigned long long hit = (__ballot(incl > rr) >> base) & (WAVE ? ~0ull : 0xFFFFull);
+  int k = cnt > 0 ? cnt - 1 : 0;                         // corrupted sums leave no run: the last valid slot
+  bool found = false;
+  if (hit != 0) {
+    const int f = __ffsll(hit) - 1;                      // the first run whose inclusive sum exceeds rr
+    uint64_t run = __shfl(incl, f, L) - __shfl(mine, f, L);
+    for (int t = 0; t < per; t++) {
+      const int kk = f * per + t;
+      const uint32_t v = kk < cnt ? pr.prio[(size_t)add_mod(start, kk, T) * n + e] : 0u;
+      run += v;
+      if (!found && run > rr && kk < cnt) {
+        found = true;
+        k = kk;
+        q = v;
+      }
+    }
+  }
+  p.e = e;
+  p.slot = add_mod(start, k, T);
+  p.k = k;
+  p.cnt = cnt;
+  p.any = true;
+  if (!found && cnt > 0) q = pr.prio[(size_t)p.slot * n + e];
   return p;
 }
 
@@ -225,9 +298,11 @@ __device__ __forceinline__ float mul_then_add(float acc, float g, float r) {
   return acc + p;
 }
 
-// NSTEP: with the `ends` bytes (rules 6 and 7 of so100_replay_push_nstep); ends is NULL otherwise
-template <bool NSTEP>
-__device__ __forceinline__ void replay_push_body(const so100_replay& h, const so100_replay_step& s, uint8_t* ends) {
+// NSTEP: with the `ends` bytes (rules 6 and 7 of so100_replay_push_nstep); ends is NULL otherwise.  PER: with the
+// priorities (rules 8 and 9 of so100_replay_push_per); prio and max_prio are not read otherwise
+template <bool NSTEP, bool PER>
+__device__ __forceinline__ void replay_push_body(const so100_replay& h, const so100_replay_step& s, uint8_t* ends,
+                                                 uint32_t* prio, const uint32_t* max_prio) {
   const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
   const int e = (int)blockIdx.x, n = h.n, T = h.T, A = h.action_dim, P = h.P;
   const int c = clampi(h.meta[e], 0, T - 1);
@@ -251,6 +326,15 @@ __device__ __forceinline__ void replay_push_body(const so100_replay& h, const so
       ends[row] = done ? 1 : 0;                          // 6.
       if (drop && k > 0) ends[(size_t)sub_mod(c, 1, T) * n + e] = 1;   // 7.
     }
+    if (PER) {
+      if (drop) {
+        prio[row] = 0u;                                  // 9.
+      } else {
+        const uint32_t top = max_prio[0];
+        prio[row] = top > 0u ? top : 1u;                 // 8.
+        prio[row2] = 0u;                                 // (T >= 2: row2 != row)
+      }
+    }
   }
   if (P > 0) {
     const uint8_t* now = s.pixels + (size_t)e * P;
@@ -273,12 +357,23 @@ __device__ __forceinline__ void replay_push_body(const so100_replay& h, const so
 }  // namespace
 
 __global__ __launch_bounds__(kRepThreads) void so100_replay_push_kernel(so100_replay h, so100_replay_step s) {
-  replay_push_body<false>(h, s, nullptr);
+  replay_push_body<false, false>(h, s, nullptr, nullptr, nullptr);
 }
 
 __global__ __launch_bounds__(kRepThreads) void so100_replay_push_nstep_kernel(so100_replay h, so100_replay_step s,
                                                                                uint8_t* ends) {
-  replay_push_body<true>(h, s, ends);
+  replay_push_body<true, false>(h, s, ends, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(kRepThreads) void so100_replay_push_per_kernel(so100_replay h, so100_replay_step s,
+                                                                             uint32_t* prio, const uint32_t* max_prio) {
+  replay_push_body<false, true>(h, s, nullptr, prio, max_prio);
+}
+
+__global__ __launch_bounds__(kRepThreads) void so100_replay_push_nstep_per_kernel(so100_replay h, so100_replay_step s,
+                                                                                   uint8_t* ends, uint32_t* prio,
+                                                                                   const uint32_t* max_prio) {
+  replay_push_body<true, true>(h, s, ends, prio, max_prio);
 }
 
 namespace {
@@ -318,9 +413,13 @@ namespace {
 // NSTEP: with the n-step window (so100_replay_sample_nstep); ns and no are not read otherwise.  The window adds one round
 // of loads to the chain that a workgroup pays before its first byte moves, whatever n_step is: the addresses of the
 // window's `ends` and reward entries follow from the pick, so the lanes read them side by side.
-template <bool NSTEP>
+// PER: with the prioritised pick (so100_replay_sample_per); pr and po are not read otherwise.  Every workgroup, the
+// image pieces' included, repeats the pick as it repeats the plain one: the float and the image workgroups of a row find
+// the same slot because they run the same function on the same arrays.
+template <bool NSTEP, bool PER>
 __device__ __forceinline__ void replay_sample_body(const so100_replay& h, const so100_replay_out& o,
                                                    const so100_replay_nstep& ns, const so100_replay_nstep_out& no,
+                                                   const so100_replay_per& pr, const so100_replay_per_out& po,
                                                    int batch, uint64_t call, unsigned row_groups, int chunks, int span) {
   const int n = h.n, A = h.action_dim, P = h.P, pad = h.pad;
   if (blockIdx.x < row_groups) {
@@ -330,7 +429,9 @@ __device__ __forceinline__ void replay_sample_body(const so100_replay& h, const 
     if (il >= batch) return;
     const size_t i = (size_t)il;
     const bool scalar = c == kRepLanes - 1;
-    const RepPick p = replay_pick<false>(h, call, i);
+    uint32_t q = 0u;
+    uint64_t mass = 0ull;
+    const RepPick p = PER ? replay_pick_per<false>(h, pr, call, i, q, mass) : replay_pick<false>(h, call, i);
     if (!p.any) {                                        // an empty buffer: zeros, nothing of the ring is read
       if (c < kRepObs) {
         o.obs[i * kRepObs + c] = 0.f;
@@ -347,6 +448,10 @@ __device__ __forceinline__ void replay_sample_body(const so100_replay& h, const 
           no.discounts[i] = 0.f;
           no.nsteps[i] = 0;
           no.last_slot[i] = -1;
+        }
+        if (PER) {
+          po.probs[i] = 0.f;
+          po.weights[i] = 0.f;
         }
       }
       return;
@@ -399,6 +504,13 @@ __device__ __forceinline__ void replay_sample_body(const so100_replay& h, const 
       no.nsteps[i] = m;
       no.last_slot[i] = last_slot;
     }
+    if (PER) {
+      // rule 6: the division in float64, one rounding to float32; the weight from the count of valid transitions
+      const float prob = (float)((double)q / (double)mass);
+      const int valid = h.prefix[n];
+      po.probs[i] = prob;
+      po.weights[i] = q != 0u ? powf((float)(valid < 0 ? 0 : valid) * prob, -pr.beta) : 0.f;
+    }
     return;
   }
   // ---- the images: a piece is `span` chunks of kChunk bytes of one output image
@@ -419,7 +531,9 @@ __device__ __forceinline__ void replay_sample_body(const so100_replay& h, const 
     const int tail0 = head + 4 * nw;
     const bool ends = grp == 0;                          // this piece also takes the row's head and tail bytes
     uint32_t* dw = (uint32_t*)(dst + head);
-    const RepPick p = replay_pick<true>(h, call, i);
+    uint32_t q = 0u;
+    uint64_t mass = 0ull;
+    const RepPick p = PER ? replay_pick_per<true>(h, pr, call, i, q, mass) : replay_pick<true>(h, call, i);
     if (!p.any) {
       if (ends && tid < head) dst[tid] = 0;
       if (ends && tail0 + tid < P) dst[tail0 + tid] = 0;
@@ -489,7 +603,8 @@ __device__ __forceinline__ void replay_sample_body(const so100_replay& h, const 
 __global__ __launch_bounds__(kRepThreads) void so100_replay_sample_kernel(so100_replay h, so100_replay_out o, int batch,
                                                                           uint64_t call, unsigned row_groups, int chunks,
                                                                           int span) {
-  replay_sample_body<false>(h, o, so100_replay_nstep{}, so100_replay_nstep_out{}, batch, call, row_groups, chunks, span);
+  replay_sample_body<false, false>(h, o, so100_replay_nstep{}, so100_replay_nstep_out{}, so100_replay_per{},
+                                   so100_replay_per_out{}, batch, call, row_groups, chunks, span);
 }
 
 __global__ __launch_bounds__(kRepThreads) void so100_replay_sample_nstep_kernel(so100_replay h, so100_replay_out o,
@@ -497,7 +612,137 @@ __global__ __launch_bounds__(kRepThreads) void so100_replay_sample_nstep_kernel(
                                                                                 so100_replay_nstep_out no, int batch,
                                                                                 uint64_t call, unsigned row_groups,
                                                                                 int chunks, int span) {
-  replay_sample_body<true>(h, o, ns, no, batch, call, row_groups, chunks, span);
+  replay_sample_body<true, false>(h, o, ns, no, so100_replay_per{}, so100_replay_per_out{}, batch, call, row_groups,
+                                  chunks, span);
+}
+
+__global__ __launch_bounds__(kRepThreads) void so100_replay_sample_per_kernel(so100_replay h, so100_replay_out o,
+                                                                              so100_replay_per pr, so100_replay_per_out po,
+                                                                              int batch, uint64_t call,
+                                                                              unsigned row_groups, int chunks, int span) {
+  replay_sample_body<false, true>(h, o, so100_replay_nstep{}, so100_replay_nstep_out{}, pr, po, batch, call, row_groups,
+                                  chunks, span);
+}
+
+__global__ __launch_bounds__(kRepThreads) void so100_replay_sample_nstep_per_kernel(
+    so100_replay h, so100_replay_out o, so100_replay_nstep ns, so100_replay_nstep_out no, so100_replay_per pr,
+    so100_replay_per_out po, int batch, uint64_t call, unsigned row_groups, int chunks, int span) {
+  replay_sample_body<true, true>(h, o, ns, no, pr, po, batch, call, row_groups, chunks, span);
+}
+
+// the priorities of each env summed over its T slots (so100_replay_per_scan, first launch): 64 envs by kSumParts parts of
+// the slots per workgroup, so that a wave's loads are 256 contiguous bytes of one slot's row; the parts meet in LDS
+constexpr int kSumParts = kRepThreads / 64;
+__global__ __launch_bounds__(kRepThreads) void so100_replay_per_sum_kernel(int n, int T, const uint32_t* __restrict__ prio,
+                                                                           uint64_t* __restrict__ sum) {
+  __shared__ uint64_t part_sum[kSumParts][64];
+  const int lane = (int)threadIdx.x & 63, part = (int)threadIdx.x >> 6;
+  const long long el = (long long)blockIdx.x * 64 + lane;
+  uint64_t acc = 0;
+  if (el < n) {
+#pragma unroll 4
+    for (int s = part; s < T; s += kSumParts) acc += prio[(size_t)s * n + (size_t)el];
+  }
+  part_sum[part][lane] = acc;
+  __syncthreads();
+  if (part == 0 && el < n) {
+    uint64_t all = 0;
+#pragma unroll
+    for (int k = 0; k < kSumParts; k++) all += part_sum[k][lane];
+    sum[el] = all;
+  }
+}
+
+// sum[0..n) <- its inclusive scan, sum[n] <- the total (so100_replay_per_scan, second launch): so100_her.hip's
+// one-workgroup scan on uint64 values, in place (a thread reads its items of a tile before any thread writes that tile's)
+constexpr int kPerScanThreads = 1024;
+constexpr int kPerScanItems = 4;
+constexpr int kPerScanTile = kPerScanThreads * kPerScanItems;
+__global__ __launch_bounds__(kPerScanThreads) void so100_replay_per_scan_kernel(int n, uint64_t* sum) {
+  __shared__ uint64_t wave_sum[2][kPerScanThreads / 64];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  uint64_t carry = 0;                                    // the sum of every tile before this one: < 2^63
+  int buf = 0;
+  for (long long t0 = 0; t0 < n; t0 += kPerScanTile, buf ^= 1) {
+    const long long i0 = t0 + (long long)tid * kPerScanItems;
+    uint64_t v[kPerScanItems];
+#pragma unroll
+    for (int k = 0; k < kPerScanItems; k++) v[k] = i0 + k < n ? sum[i0 + k] : 0ull;
+    uint64_t mine = 0;
+#pragma unroll
+    for (int k = 0; k < kPerScanItems; k++) mine += v[k];
+    uint64_t incl = mine;                                // inclusive scan of the wave's 64 sums
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const uint64_t up = __shfl_up(incl, off);
+      if (lane >= off) incl += up;
+    }
+    if (lane == 63) wave_sum[buf][wave] = incl;
+    __syncthreads();                                     // (the buffers alternate: one barrier per tile)
+    uint64_t before = 0, tile = 0;
+#pragma unroll
+    for (int w = 0; w < kPerScanThreads / 64; w++) {
+      const uint64_t ws = wave_sum[buf][w];
+      before += w < wave ? ws : 0ull;
+      tile += ws;
+    }
+    uint64_t run = carry + before + incl - mine;
+#pragma unroll
+    for (int k = 0; k < kPerScanItems; k++) {
+      run += v[k];
+      if (i0 + k < n) sum[i0 + k] = run;
+    }
+    carry += tile;
+  }
+  if (tid == 0) sum[n] = carry;
+}
+
+// the fixed-point priority of |td| (so100_replay_per_update, rule 1)
+__device__ __forceinline__ uint32_t per_priority(float td, float alpha, float eps) {
+  const float x = fmaxf(fabsf(td), 0.f);                 // (fmaxf drops a NaN)
+  const float v = rintf(powf(x + eps, alpha) * (float)SO100_REPLAY_PRIO_ONE);
+  if (!(v >= 1.f)) return 1u;
+  return v >= 4294967296.f ? 0xFFFFFFFFu : (uint32_t)v;
+}
+
+// so100_replay_per_update's two launches: phase 0 stores 0 from every applied row, phase 1 raises the slot to the row's
+// q by an integer atomic maximum, so a slot named more than once ends at the greatest q whatever the order; the wave's
+// greatest q goes to max_prio[0] by one more.  No thread leaves before the wave's shuffles
+__global__ __launch_bounds__(kRepThreads) void so100_replay_per_update_kernel(so100_replay h, so100_replay_per pr,
+                                                                              int batch,
+                                                                              const int32_t* __restrict__ env_idx,
+                                                                              const int32_t* __restrict__ slot_idx,
+                                                                              const float* __restrict__ td_abs,
+                                                                              int phase) {
+  const long long j = (long long)blockIdx.x * kRepThreads + (int)threadIdx.x;
+  const int n = h.n, T = h.T;
+  bool applied = false;
+  size_t row = 0;
+  uint32_t q = 0u;
+  if (j < batch) {
+    const int e = env_idx[j], s = slot_idx[j];
+    if (e >= 0 && e < n && s >= 0 && s < T) {
+      const int cur = clampi(h.meta[e], 0, T - 1);
+      const int cnt = clampi(h.meta[(size_t)n + e], 0, T - 1);
+      applied = sub_mod(s, sub_mod(cur, cnt, T), T) < cnt;           // s is among the env's valid slots
+      row = (size_t)s * n + e;
+    }
+  }
+  if (phase == 0) {
+    if (applied) pr.prio[row] = 0u;
+    return;
+  }
+  if (applied) {
+    q = per_priority(td_abs[j], pr.alpha, pr.eps);
+    atomicMax(&pr.prio[row], q);
+  }
+  uint32_t top = q;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint32_t other = (uint32_t)__shfl_xor((int)top, off);
+    top = other > top ? other : top;
+  }
+  if (((int)threadIdx.x & 63) == 0 && top > 0u) atomicMax(&pr.max_prio[0], top);
 }
 
 hipError_t launch_replay_push(const so100_replay& h, const so100_replay_step& st, hipStream_t s) {
@@ -517,9 +762,10 @@ hipError_t launch_replay_scan(const so100_replay& h, hipStream_t s) {
   return launch_count_scan(h.n, h.T - 1, h.meta + h.n, h.prefix, s);
 }
 
-// ns, no: NULL for the plain sample
+// ns, no: NULL for the plain sample; pr, po: NULL for the uniform pick
 static hipError_t launch_sample(const so100_replay& h, const so100_replay_out& o, const so100_replay_nstep* ns,
-                                const so100_replay_nstep_out* no, int batch, uint64_t call, hipStream_t s) {
+                                const so100_replay_nstep_out* no, const so100_replay_per* pr,
+                                const so100_replay_per_out* po, int batch, uint64_t call, hipStream_t s) {
   const unsigned row_groups = (unsigned)(((long long)batch + kRepRows - 1) / kRepRows);
   const int chunks = (h.P + kChunk - 1) / kChunk;        // 0 without images
   // a workgroup finds its row's transition once (the draw, a search of the prefix sums, the metadata: dependent loads),
@@ -529,7 +775,13 @@ static hipError_t launch_sample(const so100_replay& h, const so100_replay_out& o
   span = span < 1 ? 1 : (span > chunks ? chunks : span);
   const long long pieces = chunks > 0 ? 2ll * ((chunks + span - 1) / span) * batch : 0;
   const unsigned piece_groups = (unsigned)(pieces < (long long)kMaxPieceGroups ? pieces : (long long)kMaxPieceGroups);
-  if (ns != nullptr)
+  if (pr != nullptr && ns != nullptr)
+    hipLaunchKernelGGL(so100_replay_sample_nstep_per_kernel, dim3(row_groups + piece_groups), dim3(kRepThreads), 0, s, h,
+                       o, *ns, *no, *pr, *po, batch, call, row_groups, chunks, (int)span);
+  else if (pr != nullptr)
+    hipLaunchKernelGGL(so100_replay_sample_per_kernel, dim3(row_groups + piece_groups), dim3(kRepThreads), 0, s, h, o,
+                       *pr, *po, batch, call, row_groups, chunks, (int)span);
+  else if (ns != nullptr)
     hipLaunchKernelGGL(so100_replay_sample_nstep_kernel, dim3(row_groups + piece_groups), dim3(kRepThreads), 0, s, h, o,
                        *ns, *no, batch, call, row_groups, chunks, (int)span);
   else
@@ -540,12 +792,12 @@ static hipError_t launch_sample(const so100_replay& h, const so100_replay_out& o
 
 hipError_t launch_replay_sample(const so100_replay& h, const so100_replay_out& o, int batch, uint64_t call,
                                 hipStream_t s) {
-  return launch_sample(h, o, nullptr, nullptr, batch, call, s);
+  return launch_sample(h, o, nullptr, nullptr, nullptr, nullptr, batch, call, s);
 }
 
 hipError_t launch_replay_sample_nstep(const so100_replay& h, const so100_replay_out& o, const so100_replay_nstep& ns,
                                       const so100_replay_nstep_out& no, int batch, uint64_t call, hipStream_t s) {
-  return launch_sample(h, o, &ns, &no, batch, call, s);
+  return launch_sample(h, o, &ns, &no, nullptr, nullptr, batch, call, s);
 }
 
 hipError_t launch_replay_push_nstep(const so100_replay& h, const so100_replay_nstep& ns, const so100_replay_step& st,
@@ -560,6 +812,48 @@ hipError_t launch_replay_stage_nstep(const so100_replay& h, const so100_replay_n
   hipLaunchKernelGGL(so100_replay_stage_nstep_kernel, dim3((unsigned)h.n),
                      dim3(h.P > 0 ? kRepThreads : kRepStateThreads), 0, s, h, mask, obs, pixels, ns.ends);
   return hipGetLastError();
+}
+
+// ns: NULL without the `ends` bytes
+hipError_t launch_replay_push_per(const so100_replay& h, const so100_replay_per& pr, const so100_replay_nstep* ns,
+                                  const so100_replay_step& st, hipStream_t s) {
+  const dim3 block(h.P > 0 ? kRepThreads : kRepStateThreads);
+  if (ns != nullptr)
+    hipLaunchKernelGGL(so100_replay_push_nstep_per_kernel, dim3((unsigned)h.n), block, 0, s, h, st, ns->ends, pr.prio,
+                       pr.max_prio);
+  else
+    hipLaunchKernelGGL(so100_replay_push_per_kernel, dim3((unsigned)h.n), block, 0, s, h, st, pr.prio, pr.max_prio);
+  return hipGetLastError();
+}
+
+hipError_t launch_replay_per_scan(const so100_replay& h, const so100_replay_per& pr, hipStream_t s) {
+  if (h.n > 0) {
+    hipLaunchKernelGGL(so100_replay_per_sum_kernel, dim3((unsigned)((h.n + 63) / 64)), dim3(kRepThreads), 0, s, h.n, h.T,
+                       pr.prio, pr.sum);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(so100_replay_per_scan_kernel, dim3(1), dim3(kPerScanThreads), 0, s, h.n, pr.sum);
+  return hipGetLastError();
+}
+
+// ns, no: NULL without the n-step window
+hipError_t launch_replay_sample_per(const so100_replay& h, const so100_replay_out& o, const so100_replay_per& pr,
+                                    const so100_replay_per_out& po, const so100_replay_nstep* ns,
+                                    const so100_replay_nstep_out* no, int batch, uint64_t call, hipStream_t s) {
+  return launch_sample(h, o, ns, no, &pr, &po, batch, call, s);
+}
+
+hipError_t launch_replay_per_update(const so100_replay& h, const so100_replay_per& pr, int batch, const int32_t* env_idx,
+                                    const int32_t* slot_idx, const float* td_abs, hipStream_t s) {
+  const unsigned groups = (unsigned)(((long long)batch + kRepThreads - 1) / kRepThreads);
+  for (int phase = 0; phase < 2; phase++) {
+    hipLaunchKernelGGL(so100_replay_per_update_kernel, dim3(groups), dim3(kRepThreads), 0, s, h, pr, batch, env_idx,
+                       slot_idx, td_abs, phase);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 }  // namespace so100

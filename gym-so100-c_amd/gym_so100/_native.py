@@ -342,6 +342,40 @@ class SO100ReplayNstepOut(ctypes.Structure):
             setattr(self, name, p)
 
 
+SO100_REPLAY_PRIO_ONE = 65536    # include/so100.h: the fixed-point priority 1.0
+REPLAY_PER_ARRAYS = ("prio", "sum", "max_prio")
+REPLAY_PER_OUTPUTS = ("probs", "weights")
+
+
+class SO100ReplayPer(ctypes.Structure):
+    """Mirror of ``so100_replay_per`` (include/so100.h): the exponents of prioritised replay and its three arrays."""
+    _fields_ = [("size", ctypes.c_uint32), ("alpha", ctypes.c_float), ("beta", ctypes.c_float), ("eps", ctypes.c_float),
+                ("reserved", ctypes.c_uint32 * 2)] + [(name, _P) for name in REPLAY_PER_ARRAYS]
+
+    def __init__(self, alpha=0.6, beta=0.4, eps=1e-6, **arrays):
+        super().__init__()
+        self.size = ctypes.sizeof(SO100ReplayPer)
+        self.alpha, self.beta, self.eps = float(alpha), float(beta), float(eps)
+        for name, p in arrays.items():
+            if name not in REPLAY_PER_ARRAYS:
+                raise TypeError(f"so100_replay_per has no array {name!r}")
+            setattr(self, name, p)
+
+
+class SO100ReplayPerOut(ctypes.Structure):
+    """Mirror of ``so100_replay_per_out`` (include/so100.h): the device arrays one ``so100_replay_sample_per`` fills
+    beside those of ``so100_replay_out`` (and ``so100_replay_nstep_out``)."""
+    _fields_ = [("size", ctypes.c_uint32), ("reserved0", ctypes.c_uint32)] + [(name, _P) for name in REPLAY_PER_OUTPUTS]
+
+    def __init__(self, **outputs):
+        super().__init__()
+        self.size = ctypes.sizeof(SO100ReplayPerOut)
+        for name, p in outputs.items():
+            if name not in REPLAY_PER_OUTPUTS:
+                raise TypeError(f"so100_replay_per_out has no output {name!r}")
+            setattr(self, name, p)
+
+
 SO100_NMATERIAL = 5
 
 
@@ -491,6 +525,19 @@ def load():
     lib.so100_replay_sample_nstep.argtypes = [_P, ctypes.POINTER(SO100Replay), ctypes.POINTER(SO100ReplayNstep),
                                               ctypes.c_int, ctypes.c_uint64, ctypes.POINTER(SO100ReplayOut),
                                               ctypes.POINTER(SO100ReplayNstepOut), _P]
+    lib.so100_replay_per_bytes.argtypes = []
+    lib.so100_replay_per_out_bytes.argtypes = []
+    lib.so100_replay_per_storage_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+    lib.so100_replay_per_storage_bytes.restype = ctypes.c_int64
+    lib.so100_replay_push_per.argtypes = [_P, ctypes.POINTER(SO100Replay), ctypes.POINTER(SO100ReplayPer),
+                                          ctypes.POINTER(SO100ReplayNstep), ctypes.POINTER(SO100ReplayStep), _P]
+    lib.so100_replay_per_scan.argtypes = [_P, ctypes.POINTER(SO100Replay), ctypes.POINTER(SO100ReplayPer), _P]
+    lib.so100_replay_sample_per.argtypes = [_P, ctypes.POINTER(SO100Replay), ctypes.POINTER(SO100ReplayPer),
+                                            ctypes.POINTER(SO100ReplayNstep), ctypes.c_int, ctypes.c_uint64,
+                                            ctypes.POINTER(SO100ReplayOut), ctypes.POINTER(SO100ReplayNstepOut),
+                                            ctypes.POINTER(SO100ReplayPerOut), _P]
+    lib.so100_replay_per_update.argtypes = [_P, ctypes.POINTER(SO100Replay), ctypes.POINTER(SO100ReplayPer),
+                                            ctypes.c_int, _P, _P, _P, _P]
     lib.so100_hull_cells.argtypes = [_P, _P, _P, ctypes.c_int]
     lib.so100_hull_blocks.argtypes = [_P, _P, ctypes.c_int]
     lib.so100_hull_support_probe.argtypes = [_P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P]
@@ -518,7 +565,9 @@ def load():
                "so100_her_discard", "so100_her_scan", "so100_her_sample", "so100_replay_bytes",
                "so100_replay_step_bytes", "so100_replay_out_bytes", "so100_replay_push", "so100_replay_stage",
                "so100_replay_scan", "so100_replay_sample", "so100_replay_nstep_bytes", "so100_replay_nstep_out_bytes",
-               "so100_replay_push_nstep", "so100_replay_stage_nstep", "so100_replay_sample_nstep"):
+               "so100_replay_push_nstep", "so100_replay_stage_nstep", "so100_replay_sample_nstep",
+               "so100_replay_per_bytes", "so100_replay_per_out_bytes", "so100_replay_push_per", "so100_replay_per_scan",
+               "so100_replay_sample_per", "so100_replay_per_update"):
         getattr(lib, fn).restype = ctypes.c_int
     lib.so100_struct_sizes.argtypes = [_P, _P]
     lib.so100_struct_sizes.restype = ctypes.c_int
@@ -559,7 +608,8 @@ def load():
                        ("so100_her_out_bytes", SO100HerOut), ("so100_replay_bytes", SO100Replay),
                        ("so100_replay_step_bytes", SO100ReplayStep), ("so100_replay_out_bytes", SO100ReplayOut),
                        ("so100_replay_nstep_bytes", SO100ReplayNstep),
-                       ("so100_replay_nstep_out_bytes", SO100ReplayNstepOut)):
+                       ("so100_replay_nstep_out_bytes", SO100ReplayNstepOut),
+                       ("so100_replay_per_bytes", SO100ReplayPer), ("so100_replay_per_out_bytes", SO100ReplayPerOut)):
         if getattr(lib, fn)() != ctypes.sizeof(mirror):
             raise NativeLibraryError(f"struct layout mismatch: {fn} {getattr(lib, fn)()} vs {ctypes.sizeof(mirror)}")
     _lib = lib
@@ -600,7 +650,10 @@ EXPORTED_SYMBOLS = ("so100_abi_version", "so100_last_error", "so100_source_hash"
                     "so100_replay_step_bytes", "so100_replay_out_bytes", "so100_replay_storage_bytes",
                     "so100_replay_push", "so100_replay_stage", "so100_replay_scan", "so100_replay_sample",
                     "so100_replay_nstep_bytes", "so100_replay_nstep_out_bytes", "so100_replay_nstep_storage_bytes",
-                    "so100_replay_push_nstep", "so100_replay_stage_nstep", "so100_replay_sample_nstep")
+                    "so100_replay_push_nstep", "so100_replay_stage_nstep", "so100_replay_sample_nstep",
+                    "so100_replay_per_bytes", "so100_replay_per_out_bytes", "so100_replay_per_storage_bytes",
+                    "so100_replay_push_per", "so100_replay_per_scan", "so100_replay_sample_per",
+                    "so100_replay_per_update")
 
 
 def source_hash():

@@ -6,7 +6,8 @@ option checks, which touch no device.
 Beside it the uniform replay buffer of the arm tasks: SB3 ``DictReplayBuffer``'s storage for state and
 pixel observations, with DrQ's random-shift augmentation in the sample launch (csrc/so100_replay.hip).
 ``SO100VecEnv(uniform_replay=...)`` owns one ``UniformReplay`` (``env.uniform_replay``).  With the option ``n_step`` it
-also keeps the ``ends`` bytes and samples n-step returns."""
+also keeps the ``ends`` bytes and samples n-step returns; with the option ``prioritized`` it keeps a
+priority per transition, samples in proportion to it and takes ``update_priorities``."""
 import ctypes
 import math
 
@@ -198,10 +199,44 @@ class HerReplay:
 # the reference's SAC("MultiInputPolicy", buffer_size=50_000, batch_size=256) on {"pixels", "agent_pos"}
 # (scripts/train_sac.py): a plain DictReplayBuffer
 UNIFORM_REPLAY_DEFAULTS = dict(buffer_size=None, augment=None, seed=None)
+_FLT_MIN = 1.1754943508222875e-38
 AUGMENT_DEFAULT_PAD = 4          # DrQ's random shift: pad by 4, crop at a random offset
 # the n-step options, in a table of their own: n_step None = a buffer exactly as without them (no ``ends``, the plain
 # launches); an int (1 included) = the ``_nstep`` launches and the extra sample keys.  gamma: SB3's default
 UNIFORM_REPLAY_NSTEP_DEFAULTS = dict(n_step=None, gamma=0.99)
+# prioritised replay, in tables of their own: prioritized None / False = a buffer exactly as without the key; True = the
+# exponents below (Schaul et al.'s proportional variant); a dict with exactly those three keys = its own
+UNIFORM_REPLAY_PER_DEFAULTS = dict(prioritized=None)
+PER_DEFAULTS = dict(alpha=0.6, beta=0.4, eps=1e-6)
+
+
+def _unit(what, v):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError(f"uniform_replay: {what} {v!r} must be a number")
+    v = float(v)
+    if not (math.isfinite(v) and 0.0 <= v <= 1.0):
+        raise ValueError(f"uniform_replay: {what} {v} must be finite and in [0, 1]")
+    return v
+
+
+def per_options(prioritized):
+    """The checked value of ``prioritized``: None / False -> None (off), True -> ``PER_DEFAULTS``, a dict with exactly
+    the keys alpha, beta (finite, in [0, 1]) and eps (finite, > 0) -> a copy with floats; ValueError otherwise."""
+    if prioritized is None or prioritized is False:
+        return None
+    if prioritized is True:
+        return dict(PER_DEFAULTS)
+    if not isinstance(prioritized, dict) or set(prioritized) != set(PER_DEFAULTS):
+        raise ValueError(f"uniform_replay: prioritized {prioritized!r}: None, a bool or a dict with exactly the keys "
+                         f"{sorted(PER_DEFAULTS)}")
+    eps = prioritized["eps"]
+    if isinstance(eps, (bool, np.bool_)) or not isinstance(eps, (int, float, np.integer, np.floating)):
+        raise ValueError(f"uniform_replay: eps {eps!r} must be a number")
+    eps = float(np.float32(eps))                         # (as the device reads it: an eps that rounds to 0 is refused)
+    if not (math.isfinite(eps) and eps > 0.0):
+        raise ValueError(f"uniform_replay: eps {prioritized['eps']} must be finite and > 0 in float32")
+    return dict(alpha=_unit("alpha", prioritized["alpha"]), beta=_unit("beta", prioritized["beta"]),
+                eps=float(prioritized["eps"]))
 
 
 def nstep_window(n_step, gamma, T=None):
@@ -249,18 +284,21 @@ def uniform_replay_options(uniform_replay, num_envs=None, task="so100_cube_to_bi
     the env's arguments, for the GoalEnv (``replay=`` is its buffer), without auto-reset, for fewer than 2 slots per env
     and for an augmentation without pixel observations.  The keys ``n_step`` (1..16, at most T - 1) and ``gamma`` (finite,
     in [0, 1], default 0.99; a ValueError without ``n_step``) turn the n-step returns on: the result's ``n_step`` is None
-    without them."""
+    without them.  The key ``prioritized`` (``per_options``) turns prioritised replay on: the result's ``prioritized`` is
+    None or the checked dict(alpha=, beta=, eps=)."""
     if uniform_replay is None:
         return None
     if not isinstance(uniform_replay, dict):
         raise ValueError("uniform_replay: None or a dict(" + ", ".join(f"{k}=" for k in UNIFORM_REPLAY_DEFAULTS) + ")")
-    known = {**UNIFORM_REPLAY_DEFAULTS, **UNIFORM_REPLAY_NSTEP_DEFAULTS}
+    known = {**UNIFORM_REPLAY_DEFAULTS, **UNIFORM_REPLAY_NSTEP_DEFAULTS, **UNIFORM_REPLAY_PER_DEFAULTS}
     unknown = set(uniform_replay) - set(known)
     if unknown:
         raise ValueError(f"uniform_replay: unknown keys {sorted(unknown)}; known: {sorted(known)}")
     o = dict(UNIFORM_REPLAY_DEFAULTS)
     o["n_step"] = None
+    o.update(UNIFORM_REPLAY_PER_DEFAULTS)
     o.update(uniform_replay)
+    o["prioritized"] = per_options(o["prioritized"])
     if o["n_step"] is None:
         if "gamma" in o:
             raise ValueError("uniform_replay: gamma is the n-step window's; it needs n_step=")
@@ -343,6 +381,21 @@ class UniformReplay:
                 raise RuntimeError(f"uniform_replay: ends holds {self.ends.numel()} bytes, "
                                    f"so100_replay_nstep_storage_bytes {self.lib.so100_replay_nstep_storage_bytes(n, T)}")
             self._nstep = _native.SO100ReplayNstep(n_step=self.n_step, gamma=self.gamma, ends=_native.ptr(self.ends))
+        self.prioritized = self.o.get("prioritized")
+        self._per = None            # the priorities' record: None = the uniform pick, none of the three arrays
+        if self.prioritized is not None:
+            # (not in `store`: so100_replay_storage_bytes counts that)
+            self.prio = z(T, n, dtype=torch.int32)       # uint32 fixed point on the device; read it through prio_u32()
+            self.prio_sum = z(n + 1, dtype=torch.int64)  # uint64 on the device, < 2^63
+            self.max_prio = torch.tensor([_native.SO100_REPLAY_PRIO_ONE, 0], dtype=i32, device=d)
+            held = sum(t.numel() * t.element_size() for t in (self.prio, self.prio_sum, self.max_prio))
+            want = self.lib.so100_replay_per_storage_bytes(n, T)
+            if held != want:
+                raise RuntimeError(f"uniform_replay: the priorities hold {held} bytes, so100_replay_per_storage_bytes "
+                                   f"{want}")
+            self.alpha, self.beta, self.eps = (self.prioritized[k] for k in ("alpha", "beta", "eps"))
+            self._per = self._per_record(self.beta)
+            self._per_dirty = False  # a push or an update since the last priority scan (host side)
         self.cursor, self.count = self.store["meta"]
         self._total = self.store["prefix"][n:]
         self._rec = _native.SO100Replay(n=n, T=T, action_dim=A, planes=layout[0], H=layout[1], W=layout[2],
@@ -351,10 +404,18 @@ class UniformReplay:
         self._dirty = False         # a push since the last scan (host side: nothing waits for the device)
         self.calls = 0              # sample calls so far: the draws' counter
 
+    def _per_record(self, beta):
+        return _native.SO100ReplayPer(alpha=self.alpha, beta=beta, eps=self.eps, prio=_native.ptr(self.prio),
+                                      sum=_native.ptr(self.prio_sum), max_prio=_native.ptr(self.max_prio))
+
+    def prio_u32(self):
+        """the priorities as their unsigned values, an int64 [T, n] device tensor (a copy)"""
+        return self.prio.to(self.prio_sum.dtype) & 0xFFFFFFFF
+
     # ------------------------------------------------------------------ the env's hooks
     def after_reset(self, mask):
         """the reset envs (mask: the env's uint8 mask or None = all): their fresh observation and image are staged at
-        their cursors"""
+        their cursors (a stage moves no cursor, so the priorities stay)"""
         env = self.env
         if self._nstep is not None:
             _native.check(self.lib.so100_replay_stage_nstep(env._handle, ctypes.byref(self._rec),
@@ -372,7 +433,12 @@ class UniformReplay:
         step = _native.SO100ReplayStep(obs=P(env.obs), final_obs=P(env.final_obs), action=P(command),
                                        reward=P(env.reward), terminated=P(env.terminated), truncated=P(env.truncated),
                                        diverged=P(env.diverged), pixels=P(env.pixels), final_pixels=P(env.final_pixels))
-        if self._nstep is not None:
+        if self._per is not None:
+            _native.check(self.lib.so100_replay_push_per(env._handle, ctypes.byref(self._rec), ctypes.byref(self._per),
+                                                         None if self._nstep is None else ctypes.byref(self._nstep),
+                                                         ctypes.byref(step), env._stream()), "so100_replay_push_per")
+            self._per_dirty = True
+        elif self._nstep is not None:
             _native.check(self.lib.so100_replay_push_nstep(env._handle, ctypes.byref(self._rec),
                                                            ctypes.byref(self._nstep), ctypes.byref(step),
                                                            env._stream()), "so100_replay_push_nstep")
@@ -387,6 +453,11 @@ class UniformReplay:
             _native.check(self.lib.so100_replay_scan(self.env._handle, ctypes.byref(self._rec), self.env._stream()),
                           "so100_replay_scan")
             self._dirty = False
+        if self._per is not None and self._per_dirty:
+            _native.check(self.lib.so100_replay_per_scan(self.env._handle, ctypes.byref(self._rec),
+                                                         ctypes.byref(self._per), self.env._stream()),
+                          "so100_replay_per_scan")
+            self._per_dirty = False
 
     @property
     def valid_count(self):
@@ -398,7 +469,29 @@ class UniformReplay:
         """``valid_count`` on the host (waits for the device)"""
         return int(self.valid_count.item())
 
-    def sample(self, batch_size, augment=None, normalize=False, check=False, n_step=None, gamma=None):
+    def update_priorities(self, env, slot, td_abs):
+        """The priorities of the transitions (env[j], slot[j]) from |TD error| td_abs[j]: device tensors of one length
+        (int32, int32, float32; other dtypes are converted), usually a batch's ``env`` and ``slot``.  q = (|td| +
+        eps)^alpha in fixed point; a slot named more than once takes the greatest; rows whose transition has left the
+        ring since (and the slot -1 of an empty-buffer row) are skipped, a slot overwritten since takes the value.
+        Nothing waits for the device.  ValueError on a buffer built without ``prioritized``."""
+        import torch
+        if self._per is None:
+            raise ValueError("uniform_replay: update_priorities needs a buffer built with prioritized=")
+        d = self.env.device
+        cols = [torch.as_tensor(t, device=d).reshape(-1).to(dt).contiguous()
+                for t, dt in ((env, torch.int32), (slot, torch.int32), (td_abs, torch.float32))]
+        B = cols[0].numel()
+        if cols[1].numel() != B or cols[2].numel() != B:
+            raise ValueError(f"uniform_replay: update_priorities takes three tensors of one length, got "
+                             f"{[c.numel() for c in cols]}")
+        if B:
+            _native.check(self.lib.so100_replay_per_update(self.env._handle, ctypes.byref(self._rec),
+                                                           ctypes.byref(self._per), B, *[_native.ptr(c) for c in cols],
+                                                           self.env._stream()), "so100_replay_per_update")
+            self._per_dirty = True
+
+    def sample(self, batch_size, augment=None, normalize=False, check=False, n_step=None, gamma=None, beta=None):
         """A batch of ``batch_size`` transitions as a dict of device tensors.  Pixel env: ``pixels`` / ``next_pixels``
         ([B, *env.pixels.shape[1:]] uint8), ``agent_pos`` / ``next_agent_pos`` (columns 9:15 of the state rows) and
         ``state`` / ``next_state`` (the 15-float rows); state env: ``obs`` / ``next_obs``.  Both: ``actions``,
@@ -412,7 +505,10 @@ class UniformReplay:
         ``n_steps`` (m, the transitions of the row's window) and ``last_slot``; ``rewards`` is then the discounted sum
         over the window, and ``dones`` and the ``next_`` entries are those of its last transition.  n_step, gamma:
         another window for this call (the ``ends`` bytes are stored regardless); ValueError on a buffer built without
-        ``n_step``."""
+        ``n_step``.
+        A buffer built with ``prioritized`` draws each row with probability ``probs`` (its priority over the sum) and
+        also returns ``weights``, the importance weights (count * probs)^-beta divided by the batch's greatest.  beta:
+        another exponent for this call (annealing); ValueError on a buffer built without ``prioritized``."""
         import torch
         B = _int("batch_size", batch_size)
         if B < 0:
@@ -424,6 +520,11 @@ class UniformReplay:
         else:
             window = nstep_window(self.n_step if n_step is None else n_step, self.gamma if gamma is None else gamma,
                                   self.T)
+        if self._per is None:
+            if beta is not None:
+                raise ValueError("uniform_replay: sample(beta=) needs a buffer built with prioritized=")
+        else:
+            beta = self.beta if beta is None else _unit("beta", beta)
         pad = self.pad if augment is None else augment_pad(augment)
         if pad > 0 and not self.P:
             raise ValueError("uniform_replay: augment shifts images; it needs obs_type='so100_pixels_agent_pos'")
@@ -440,7 +541,29 @@ class UniformReplay:
             raw["pixels"] = e(B, *self.image_shape, dtype=torch.uint8)
             raw["next_pixels"] = e(B, *self.image_shape, dtype=torch.uint8)
         rec = _native.SO100ReplayOut(**{k: _native.ptr(t) for k, t in raw.items()})
-        if self._nstep is not None:
+        if self._per is not None:
+            more = {"discounts": e(B), "nsteps": e(B, dtype=i32), "last_slot": e(B, dtype=i32)} \
+                if self._nstep is not None else {}
+            pout = {"probs": e(B), "weights": e(B)}
+            if B:
+                self._rec.pad = pad
+                ns = nrec = None
+                if self._nstep is not None:
+                    ns = ctypes.byref(_native.SO100ReplayNstep(n_step=window[0], gamma=window[1],
+                                                               ends=_native.ptr(self.ends)))
+                    nrec = ctypes.byref(_native.SO100ReplayNstepOut(**{k: _native.ptr(t) for k, t in more.items()}))
+                prec = _native.SO100ReplayPerOut(**{k: _native.ptr(t) for k, t in pout.items()})
+                per = self._per_record(beta)
+                _native.check(self.lib.so100_replay_sample_per(env._handle, ctypes.byref(self._rec), ctypes.byref(per),
+                                                               ns, B, ctypes.c_uint64(self.calls), ctypes.byref(rec),
+                                                               nrec, ctypes.byref(prec), env._stream()),
+                              "so100_replay_sample_per")
+            if more:
+                raw["discounts"], raw["n_steps"], raw["last_slot"] = more["discounts"], more["nsteps"], more["last_slot"]
+            # the common batch-max normalisation: two ops, no synchronisation (an empty buffer's zeros stay zeros)
+            raw["probs"] = pout["probs"]
+            raw["weights"] = pout["weights"] / pout["weights"].max().clamp_min(_FLT_MIN) if B else pout["weights"]
+        elif self._nstep is not None:
             more = {"discounts": e(B), "nsteps": e(B, dtype=i32), "last_slot": e(B, dtype=i32)}
             if B:
                 self._rec.pad = pad

@@ -473,6 +473,12 @@ ReplaySamples = collections.namedtuple("ReplaySamples",
 # the same five and the factor of the bootstrap value, gamma^m, for a buffer built with n_step: what a learner with
 # n-step targets reads from its samples
 NStepReplaySamples = collections.namedtuple("NStepReplaySamples", ReplaySamples._fields + ("discounts",))
+# a buffer built with prioritized: the importance weights [B, 1] (divided by the batch's greatest) and what
+# update_priorities takes back, after the fields above
+_PER_FIELDS = ("weights", "env_indices", "slot_indices")
+PrioritizedReplaySamples = collections.namedtuple("PrioritizedReplaySamples", ReplaySamples._fields + _PER_FIELDS)
+PrioritizedNStepReplaySamples = collections.namedtuple("PrioritizedNStepReplaySamples",
+                                                       NStepReplaySamples._fields + _PER_FIELDS)
 
 
 class SO100ReplayBuffer(_ReplayBufferBase):
@@ -483,7 +489,10 @@ class SO100ReplayBuffer(_ReplayBufferBase):
     images) on the device and returns torch tensors there.  SB3's own storage is never allocated (its ``__init__`` is
     not run).  ``n_steps`` and ``gamma``, which a learner with n-step targets passes to its buffer, are ignored for an
     env built without ``uniform_replay=dict(n_step=...)``; with it they must agree with the env's options (ValueError
-    otherwise), and ``sample`` returns ``NStepReplaySamples``: the five fields and ``discounts`` [B, 1]."""
+    otherwise), and ``sample`` returns ``NStepReplaySamples``: the five fields and ``discounts`` [B, 1].  For an env built
+    with ``uniform_replay=dict(prioritized=...)`` the samples also carry ``weights`` [B, 1],
+    ``env_indices`` and ``slot_indices`` [B], and ``update_priorities`` takes the two index fields back with |TD error|.
+    Nothing is claimed about SB3's own classes: a learner that uses these fields reads them by name."""
 
     def __init__(self, buffer_size=None, observation_space=None, action_space=None, env=None, device="auto", n_envs=None,
                  n_steps=None, gamma=None, **_ignored):
@@ -525,9 +534,23 @@ class SO100ReplayBuffer(_ReplayBufferBase):
             nxt = {"pixels": b["next_pixels"], "agent_pos": b["next_agent_pos"]}
         else:
             obs, nxt = b["obs"], b["next_obs"]
+        if "weights" in b:
+            more = dict(weights=b["weights"].reshape(-1, 1), env_indices=b["env"], slot_indices=b["slot"])
+            if "discounts" in b:
+                return PrioritizedNStepReplaySamples(observations=obs, actions=b["actions"], next_observations=nxt,
+                                                     dones=b["dones"].reshape(-1, 1),
+                                                     rewards=b["rewards"].reshape(-1, 1),
+                                                     discounts=b["discounts"].reshape(-1, 1), **more)
+            return PrioritizedReplaySamples(observations=obs, actions=b["actions"], next_observations=nxt,
+                                            dones=b["dones"].reshape(-1, 1), rewards=b["rewards"].reshape(-1, 1), **more)
         if "discounts" in b:
             return NStepReplaySamples(observations=obs, actions=b["actions"], next_observations=nxt,
                                       dones=b["dones"].reshape(-1, 1), rewards=b["rewards"].reshape(-1, 1),
                                       discounts=b["discounts"].reshape(-1, 1))
         return ReplaySamples(observations=obs, actions=b["actions"], next_observations=nxt,
                              dones=b["dones"].reshape(-1, 1), rewards=b["rewards"].reshape(-1, 1))
+
+    def update_priorities(self, env_indices, slot_indices, td_abs):
+        """|TD error| of a sampled batch back into the priorities (``UniformReplay.update_priorities``); ValueError for an
+        env built without ``uniform_replay=dict(prioritized=...)``"""
+        self.replay.update_priorities(env_indices, slot_indices, td_abs)

@@ -297,7 +297,11 @@ class SO100VecEnv:
             (default 0.99) turns on n-step returns: push and reset then also record where episodes
             end (a done, a ``reset(mask)`` in mid-episode, a dropped step), and ``sample`` sums the discounted rewards
             over a window that stays within one episode and gains the keys ``discounts``, ``n_steps`` and
-            ``last_slot``.  Without the key nothing changes.
+            ``last_slot``.  Without the key nothing changes.  ``prioritized`` (None / False, True = alpha 0.6, beta
+            0.4, eps 1e-6, or dict(alpha=, beta=, eps=)) turns on proportional prioritised replay: a
+            new transition takes the greatest priority so far, ``sample`` draws in proportion to the priorities and
+            gains ``probs`` and ``weights``, and ``uniform_replay.update_priorities(env, slot, td_abs)`` sets them from
+            |TD error|.  It composes with ``n_step``; without the key nothing changes.
     """
 
     def __init__(self, num_envs, task="so100_cube_to_bin", obs_type="so100_state", device="cuda:0", seed=0,

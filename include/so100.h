@@ -894,6 +894,106 @@ int so100_replay_sample_nstep(so100_env* env, const so100_replay* replay, const 
                               uint64_t call, const so100_replay_out* out, const so100_replay_nstep_out* nout,
                               void* stream);
 
+/* ---- (additions to ABI 25) prioritised replay in the uniform replay buffer: proportional
+ * prioritisation (Schaul et al.), for the plain and the n-step buffer alike.  Only the pick changes: a transition is
+ * drawn with probability q / total, q its priority.  Three more caller-owned arrays, named by so100_replay_per beside
+ * so100_replay (and so100_replay_nstep); so100_replay, so100_replay_nstep, so100_replay_out and the entry points above
+ * keep their meaning.
+ *
+ * Priorities are integers: uint32 fixed point, SO100_REPLAY_PRIO_ONE = 65536 is the priority 1.0.  A valid transition's
+ * lies in 1 .. 2^32 - 1, every slot that holds none has 0.  Sums are uint64 (T n < 2^31 slots of < 2^32 stay below
+ * 2^63): exact and associative, so a scan in any order gives the same bits.
+ *   prio      uint32 [T][n], slot-major, zero at the start.  After every launch below: prio[s][e] > 0 exactly when slot s
+ *             of env e is one of the env's count[e] valid transitions.
+ *   sum       uint64 [n + 1]: sum[e] = the priorities of the envs 0..e, sum[n] = the total (so100_replay_per_scan).
+ *   max_prio  uint32 [2], word 0 used, SO100_REPLAY_PRIO_ONE at the start: the greatest priority ever applied.
+ *
+ * so100_replay_push_per (one launch: so100_replay_push's kernel, or so100_replay_push_nstep's when nstep is given,
+ *   compiled once more with the priorities): rules 1-5 (and 6, 7) of the push, and in the same workgroup, by the thread
+ *   that writes the scalars, with c, c' the cursor before and after:
+ *   8. a stored step: prio[c] <- max(max_prio[0], 1) (a new transition is drawn at least once soon), then prio[c'] <- 0:
+ *      c' is now the staged slot; in a full ring it held the oldest transition, which thereby leaves the sum.
+ *   9. a dropped step (diverged[e] non-zero): prio[c] <- 0.
+ *   so100_replay_stage / so100_replay_stage_nstep move neither cursor nor count: they serve this buffer as they are.
+ * so100_replay_per_scan (two launches: the per-env sums read T n words with the whole device, the scan over the envs
+ *   is one workgroup's, and nothing in this file waits for another workgroup): sum as defined above, recomputed from
+ *   prio every time.  so100_replay_scan stays the scan of the counts, which the weights need.
+ * so100_replay_sample_per, batch element i (one launch: so100_replay_sample's kernel, or so100_replay_sample_nstep's,
+ *   with this pick compiled in; it reads sum and prefix, so both scans must follow the last push or update):
+ *   1. total = sum[n]; total == 0: the rows of so100_replay_sample's empty buffer (and of so100_replay_sample_nstep's),
+ *      probs[i] = 0, weights[i] = 0.  Else
+ *   2. r = floor(draw(0) * total / 2^64): the draw field of the plain pick, exactly uniform on [0, total).
+ *   3. e = the first env with sum[e] > r (n - 1 if corrupted sums leave none).
+ *   4. rr = r - sum[e-1] (sum[-1] = 0); the valid slots oldest first, k = 0 .. count[e] - 1 from (cursor[e] - count[e])
+ *      mod T: the pick is the first k whose running sum of priorities exceeds rr; if corrupted sums leave none, the last
+ *      valid slot (count[e] == 0, which only corrupted arrays reach: k = 0, the slot at the cursor).  q = its priority.
+ *   5. Everything downstream (the gathered rows, the shifts, the n-step window from (slot, k, count[e])) is the plain
+ *      sample's from that pick.  With all valid priorities equal the pick is the plain pick bit for bit:
+ *      floor(floor(h c M / 2^64) / c) = floor(h M / 2^64).
+ *   6. probs[i] = (float)((double)q / (double)total), both conversions and the division correctly rounded;
+ *      weights[i] = powf((float)prefix[n] * probs[i], -beta) (prefix[n] the count of valid transitions), un-normalised
+ *      (0 where q == 0).  The caller divides by the batch maximum.
+ * so100_replay_per_update (two launches of one kernel), row j of `batch`, e = env_idx[j], s = slot_idx[j]:
+ *   1. x = fmaxf(fabsf(td_abs[j]), 0) (a NaN counts as 0); q = rintf(powf(x + eps, alpha) * 65536) clamped into
+ *      1 .. 2^32 - 1 (inf saturates), in float32.
+ *   2. The row is ignored when e is outside 0..n-1, s outside 0..T-1 (the -1 of an empty-buffer row included), or s is
+ *      not among env e's valid slots now: a transition evicted since the sample is skipped; a slot overwritten since
+ *      takes the value.
+ *   3. Sampling is with replacement, so a batch names the same slot more than once: the slot gets the greatest q
+ *      written to it in the call.  The first launch stores 0 from every applied row, the second does an integer
+ *      atomic maximum from every applied row.
+ *   4. max_prio[0] <- max(max_prio[0], q) over the applied rows: one atomic per wave after a wave reduction.
+ *   The integer maximum is commutative and associative: the result is a function of the inputs alone.  These are the
+ *   library's only atomics; there are no float atomics.
+ * Every index read from memory is clamped into its range before it addresses anything. */
+#define SO100_REPLAY_PRIO_ONE 65536u
+typedef struct so100_replay_per {
+  uint32_t  size;           /* sizeof(so100_replay_per) */
+  float     alpha;          /* (update) finite, in [0, 1] */
+  float     beta;           /* (sample) finite, in [0, 1] */
+  float     eps;            /* (update) finite, > 0 */
+  uint32_t  reserved[2];
+  uint32_t* prio;           /* [T][n] */
+  uint64_t* sum;            /* [n + 1] */
+  uint32_t* max_prio;       /* [2] */
+} so100_replay_per;
+int so100_replay_per_bytes(void);
+/* The additional outputs of one so100_replay_sample_per call: device arrays of `batch` rows. */
+typedef struct so100_replay_per_out {
+  uint32_t size;            /* sizeof(so100_replay_per_out) */
+  uint32_t reserved0;
+  float*   probs;           /* [B]: q / total */
+  float*   weights;         /* [B]: (count * probs)^-beta, un-normalised */
+} so100_replay_per_out;
+int so100_replay_per_out_bytes(void);
+/* Bytes of prio, sum and max_prio together: 4 T n + 8 (n + 1) + 8, in 64-bit arithmetic; -1 (text in so100_last_error)
+ * for n < 0, T < 2 or T * n >= 2^31.  so100_replay_storage_bytes does not count them. */
+int64_t so100_replay_per_storage_bytes(int n, int T);
+/* All four: launches on `stream`, no allocation, no synchronisation; nothing launched for n = 0 (push, update) or
+ * batch = 0 (sample, update).  Nonzero (text in so100_last_error) before any device work and with nothing written, in
+ * this order:
+ *   1. the numbers of so100_replay, as so100_replay_push refuses them (NULL replay .. pad);
+ *   2. NULL per, a wrong `size` of it;
+ *   3. an alpha or a beta that is not finite or outside [0, 1];
+ *   4. an eps that is not finite or <= 0;
+ *   5. (nstep given) a wrong `size` of it, its n_step, its gamma, as so100_replay_push_nstep refuses them;
+ *   6. (sample) nout without nstep, nstep without nout, a wrong `size` of nout;
+ *   7. (sample) NULL pout, a wrong `size` of it;
+ *   8. (push) NULL step or a wrong `size`; (sample) NULL out or a wrong `size`; (sample, update) batch < 0;
+ *   9. a NULL env, the arrays of so100_replay as so100_replay_push refuses them, (nstep given) NULL ends, then NULL
+ *      prio, sum or max_prio, then the pointers of step, out, nout and pout as their own calls refuse them, (update)
+ *      NULL env_idx, slot_idx or td_abs. */
+int so100_replay_push_per(so100_env* env, const so100_replay* replay, const so100_replay_per* per,
+                          const so100_replay_nstep* nstep /* or NULL */, const so100_replay_step* step, void* stream);
+int so100_replay_per_scan(so100_env* env, const so100_replay* replay, const so100_replay_per* per, void* stream);
+int so100_replay_sample_per(so100_env* env, const so100_replay* replay, const so100_replay_per* per,
+                            const so100_replay_nstep* nstep /* or NULL */, int batch, uint64_t call,
+                            const so100_replay_out* out, const so100_replay_nstep_out* nout /* NULL without nstep */,
+                            const so100_replay_per_out* pout, void* stream);
+int so100_replay_per_update(so100_env* env, const so100_replay* replay, const so100_replay_per* per, int batch,
+                            const int32_t* env_idx /* [B] */, const int32_t* slot_idx /* [B] */,
+                            const float* td_abs /* [B] */, void* stream);
+
 /* Batched sparse GoalEnv reward (env.py:341-353): out[i] = ||a_i - d_i|| < threshold ? 0 : -1. */
 int so100_goal_reward(so100_env* env, int n, const float* achieved, const float* desired, float* out,
                       void* stream);
